@@ -239,10 +239,12 @@ def build_step(cfg, shard, device, world=1, collective=False):
         """One step as M micro-batches (config 4): gradients summed in ``total``, each slice's mean loss weighted 1 / M."""
         finish()
         loss = None
+        step.last_pred_c = []                                  # per micro-batch (views: no launch)
         for i, part in enumerate(parts):
             pattern, graph = batch_of(part)
             sync.detach_grads()
             out = model(pattern, graph)
+            step.last_pred_c.append(out["pred_c"].detach())
             loss = torch.nn.functional.mse_loss(out["pred_c"].view(-1), part["counts"]) / M
             loss.backward()
             del out, pattern, graph
@@ -283,6 +285,7 @@ def build_step(cfg, shard, device, world=1, collective=False):
             keep = read_all(out)                               # alive until the backward has run
         else:
             out = model(pattern, graph)
+        step.last_pred_c = out["pred_c"].detach()            # what --dump-outputs writes (a view: no launch)
         loss = count_loss(out["pred_c"].view(-1), shard["counts"])  # count loss (train.py:624-628; harness.count_loss: criterion + mean + seed in one launch)
         loss.backward()
         if all_outputs:
@@ -840,6 +843,28 @@ def spawn_ranks(n, argv):
     return rc
 
 
+DUMP_MAX_ELEMS = 1 << 22      # --dump-outputs: at most 16 MB per array, 64 MB for the four
+
+
+def last_step_outputs(step, loss):
+    """Device copies of what the step just run handed back (loss, predicted counts) and left behind (flat gradient, flat
+    parameters after the optimizer update)."""
+    pred = step.last_pred_c
+    pred = torch.cat([p.reshape(-1) for p in pred]) if isinstance(pred, list) else pred.reshape(-1)
+    return {"loss": loss.detach().reshape(-1).clone(), "pred_c": pred.clone(), "grad": step.sync.flat.detach().clone(),
+            "params": step.sync.master.detach().clone()}
+
+
+def write_outputs(path, outs):
+    """``outs`` as ``path/<name>.npy`` in float32; an array over DUMP_MAX_ELEMS elements as a fixed, seeded sample of them."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in outs.items():
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def profiler_attached():
     """rocprofv3 (or another tool that preloads into this process) is driving the run."""
     return any(k.startswith(("ROCPROF", "ROCP_", "ROCTRACER")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
@@ -922,6 +947,10 @@ def main():
     ap.add_argument("--dump-grad", default=None, metavar="PATH",
                     help="testing aid: before the warm-up, one forward + backward + gradient pack + all-reduce (averaged) from "
                          "the initial parameters; rank 0 saves the flat gradient and its own shard's predictions to PATH")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the run, rank 0 writes what the LAST timed step computed as DIR/<name>.npy (float32): loss, "
+                         "pred_c (the predicted counts), grad (the flat gradient), params (the flat parameters after the "
+                         "optimizer update); an array over %d elements is a fixed, seeded sample of them" % DUMP_MAX_ELEMS)
     ap.add_argument("--emulate-world", type=int, default=1, metavar="W",
                     help="testing aid (one process): the batch is the shards of ranks 0..W-1 back to back -- the global batch "
                          "of a W-rank run")
@@ -933,6 +962,8 @@ def main():
                     help="testing aid (runs without a GPU): start the ranks, form the process group, count them with an "
                          "all-reduce and print a line with n_gpus / ranks_seen and value null -- no step is run")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step (--steps 1 or more)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process becomes the parent of N fresh rank processes and never touches the GPU itself
@@ -1104,16 +1135,21 @@ def main():
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     del step.ar_events[:]
     host_s = 0.0                                             # host time inside run(): enqueue (and, with gloo, the blocking collective)
+    loss = None
     t0 = time.perf_counter()
     for i in range(args.steps):
         marks[i].record()
         h0 = time.perf_counter()
-        run()
+        loss = run()
         host_s += time.perf_counter() - h0
     step.finish()                                            # the last step's all-reduce + optimizer update: inside the timed region
     marks[args.steps].record()
     barrier()
     dt = time.perf_counter() - t0
+    # the last timed step's results, copied on the device now (later steps overwrite them) and written at the end of the run
+    # (a blocking device-to-host copy between two recordings is what StepGraph warns against)
+    dumped = last_step_outputs(step, loss) if (args.dump_outputs and rank == 0) else None
+    loss = None                                              # no step's autograd history is kept across later recordings
     per_step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)) if args.steps else []
     step.time_allreduce = False
     ar_ms = [a.elapsed_time(b) for a, b in step.ar_events]
@@ -1483,6 +1519,8 @@ def main():
                 raise
             line["rate_check"] = "FAILED: " + str(e).splitlines()[0][:300]
             print(str(e), file=sys.stderr, flush=True)
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
         print(json.dumps(line), flush=True)
     if multi:
         dist.barrier()

@@ -107,6 +107,31 @@ def test_default_mode_replays_and_eager_agrees(gpu):
     assert g["config"]["launch"].startswith("one HIP graph replay per step")
 
 
+def test_dump_outputs_holds_the_last_timed_step(gpu, tmp_path):
+    """``--dump-outputs DIR``: the last timed step's loss, predictions, flat gradient and flat parameters as float32 ``.npy``;
+    the replayed step (default mode) and eager launches dump the same step, one more timed step dumps a different one."""
+    import numpy as np
+    # (--warmup 3: the replayed mode warms up with at least 3 steps -- eager, record + replay, replay -- so both runs take as many)
+    fast = ("--warmup", "3", "--no-cpu-baseline", "--no-all-outputs", "--no-gate-compact", "--no-gate-dense", "--extended-steps", "0")
+    runs = {"default": (), "eager": ("--eager",), "eager4": ("--eager", "--steps", "4")}
+    dumps = {}
+    for name, flags in runs.items():
+        out = tmp_path / name
+        d = _run(*fast, *flags, "--dump-outputs", str(out))
+        assert d["steps"] == (4 if name == "eager4" else 3) and d["ms_per_step"] > 0
+        assert d["launch_mode"] == ("hip_graph_replay" if name == "default" else "eager")
+        assert sorted(os.listdir(out)) == ["grad.npy", "loss.npy", "params.npy", "pred_c.npy"]
+        a = dumps[name] = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+        assert all(v.dtype == np.float32 and v.ndim == 1 and np.isfinite(v).all() for v in a.values())
+        assert a["loss"].shape == (1,) and a["pred_c"].shape == (16,) and a["grad"].shape == a["params"].shape
+        assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k, x in dumps["default"].items():
+        y = dumps["eager"][k]
+        scale = max(1.0, float(np.abs(y).max()))
+        assert float(np.abs(x.astype(np.float64) - y).max()) <= 1e-4 * scale, k
+    assert not np.array_equal(dumps["eager"]["params"], dumps["eager4"]["params"])
+
+
 def test_cpu_baseline_object(gpu):
     d = _run("--eager", timeout=900)
     c = d["cpu_baseline"]
