@@ -18,10 +18,24 @@ class Identity(nn.Module):
         return x
 
 
+class Sparsemax(nn.Module):
+    """utils/act.py:255-316: the Euclidean projection onto the simplex along ``dim`` (tensor ops: ``attn.sparsemax``).
+    ``dim`` is an attribute: the attention modules set it on the shared instance, as the reference's do."""
+
+    def __init__(self, dim=-1):
+        super(Sparsemax, self).__init__()
+        self.dim = dim
+
+    def forward(self, x):
+        from .attn import sparsemax
+        return sparsemax(x, self.dim)
+
+
 # utils/act.py:457-474 -- module-level singletons, shared by every layer that asks for them
 supported_act_funcs = {
     "none": Identity(),
     "softmax": nn.Softmax(dim=-1),
+    "sparsemax": Sparsemax(dim=-1),
     "sigmoid": nn.Sigmoid(),
     "tanh": nn.Tanh(),
     "relu": nn.ReLU(),
@@ -88,7 +102,24 @@ _INITS = {
     "uniform": lambda x, gain: nn.init.uniform_(x, -_glorot_bound(x, gain), _glorot_bound(x, gain)),
     "normal": lambda x, gain: nn.init.normal_(x, 0, gain / math.sqrt(_fans(x)[0])),
     "orthogonal": lambda x, gain: nn.init.orthogonal_(x, gain=1.0),      # the reference ignores the gain here
+    "identity": lambda x, gain: _identity_init(x, gain),
 }
+
+
+def _identity_init(x, gain):
+    """utils/init.py:105-122: ones (1-D) or the identity (2-D) plus ``randn_like(x) * std ** 2`` with
+    std = gain * 2 / (fan_in + fan_out) -- the square on std is the reference's; one randn_like draw per tensor."""
+    with th.no_grad():
+        if x.dim() > 2:
+            _identity_init(x.view(tuple(x.size())[:-2] + (-1,)), gain)
+            return x
+        std = gain * (2.0 / float(sum(_fans(x))))
+        if x.dim() == 1:
+            nn.init.ones_(x)
+        else:
+            nn.init.eye_(x)
+        x += th.randn_like(x) * std ** 2
+    return x
 
 
 def xavier_uniform_init(x, gain=1.0):
@@ -124,6 +155,7 @@ _EMBEDDING_INITS = {
     "uniform": lambda w: nn.init.uniform_(w, -1.0, 1.0),
     "normal": lambda w: nn.init.normal_(w, 0.0, 1.0),
     "orthogonal": lambda w: nn.init.orthogonal_(w, gain=math.sqrt(_fans(w)[0])),
+    "identity": lambda w: nn.init.eye_(w),
 }
 _WEIGHTED = (nn.Linear, nn.Conv1d, nn.Conv2d, nn.Conv3d)
 _NORMS = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.LayerNorm, nn.GroupNorm)

@@ -24,7 +24,7 @@ from .graph import as_batched
 from .dmpnn import DMPNNRepMixin
 from .embed import (EquivariantEmbedding, MultihotEmbedding, NormalEmbedding, OrthogonalEmbedding,
                     PositionEmbedding, UniformEmbedding, get_enc_len, lookup_rows)
-from .pred import PRED_NETS
+from .pred import PRED_NETS, pred_net_kwargs
 from .rgnn import RGCNRepMixin, RGINRepMixin
 
 
@@ -499,7 +499,7 @@ class GraphAdjModel(BaseModel):
             raise NotImplementedError("pred_net=%s is outside the MI355X hot-path scope" % name)
         return PRED_NETS[name](self.get_rep_dim(), hidden_dim=kw.get("pred_hid_dim", 64),
                                act_func=kw.get("pred_act_func", "relu"), dropout=kw.get("pred_dropout", 0.0),
-                               return_weights="node" in kw.get("pred_return_weights", "none"))
+                               return_weights="node" in kw.get("pred_return_weights", "none"), **pred_net_kwargs(name, kw))
 
     def _enc_dims(self, nv, nvl):
         return OrderedDict({"v": int(get_enc_len(nv - 1, self.base)) * self.base,
@@ -653,7 +653,7 @@ class GraphAdjModelV2(BaseModel):
         return_weights = kw.get("pred_return_weights", "none")
         rep_v_dim, rep_e_dim = self.get_rep_dim()
         args = dict(hidden_dim=kw.get("pred_hid_dim", 64), act_func=kw.get("pred_act_func", "relu"),
-                    dropout=kw.get("pred_dropout", 0.0))
+                    dropout=kw.get("pred_dropout", 0.0), **pred_net_kwargs(name, kw))
         return nn.ModuleDict({
             "v": PRED_NETS[name](rep_v_dim, return_weights="node" in return_weights, **args) if self.node_pred else None,
             "e": PRED_NETS[name](rep_e_dim, return_weights="edge" in return_weights, **args) if self.edge_pred else None,

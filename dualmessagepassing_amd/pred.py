@@ -1,10 +1,11 @@
-"""Pooling prediction heads of the model skeleton -- ``SubgraphCountingMatching/models/pred.py:17-233``
-(``PredictNet`` and its Mean / Sum / Max variants; the attention / memory heads are out of scope).
-Dense ``[B, *]`` work after the representations have been pooled per graph."""
+"""Prediction heads of the model skeleton -- ``SubgraphCountingMatching/models/pred.py:17-233`` (``PredictNet`` and its
+Mean / Sum / Max pooling variants: dense ``[B, *]`` work after the representations have been pooled per graph) and
+pred.py:240-643 (the gated sparsemax ``DotAttention`` and the Sum / Mean / Max attention heads over the padded rows;
+the memory / DIAM heads are out of scope)."""
 import torch as th
 import torch.nn as nn
 
-from .act import init_module, map_activation_str_to_layer
+from .act import init_module, init_weight, map_activation_str_to_layer
 
 
 class _PooledHead(th.autograd.Function):
@@ -322,4 +323,101 @@ class MaxPredictNet(PredictNet):
         return th.max(g_rep, dim=1)[0]
 
 
-PRED_NETS = {"MeanPredictNet": MeanPredictNet, "SumPredictNet": SumPredictNet, "MaxPredictNet": MaxPredictNet}
+class DotAttention(nn.Module):
+    """``DotAttention`` with ``add_gate=True`` as the attention heads build it (pred.py:240-487): no dropout, no layer
+    norm, no residual, sparsemax scores over the key axis.
+
+        q, k, v = query W_q, key W_k, value W_v (split into heads);  a = sparsemax(scale q k^T) v  (query-masked rows 0)
+        a = a W_o;  g = sigmoid(g_net([query, a]));  out = g query + (1 - g) a
+
+    Parameters, their registration order and their initialisers are the reference's (``parameters()`` order
+    weight_v, weight_o, weight_q, weight_k, g_net.weight, g_net.bias).  The projections and the gate are torch GEMMs;
+    the attention core is ``attn.sparsemax_attention`` (the HIP kernels of csrc/dmp_attn.hip on the GPU)."""
+
+    def __init__(self, query_dim, key_dim, value_dim, hidden_dim, num_heads=1, scale=1.0, score_func="sparsemax"):
+        super(DotAttention, self).__init__()
+        if hidden_dim % num_heads != 0:
+            raise ValueError("Error: hidden_dim (%d) %% num_heads (%d) should be 0." % (hidden_dim, num_heads))
+        if score_func != "sparsemax":
+            raise NotImplementedError("DotAttention score_func=%s is outside the MI355X hot-path scope" % score_func)
+        self.query_dim, self.key_dim, self.value_dim, self.hidden_dim = query_dim, key_dim, value_dim, hidden_dim
+        self.num_heads, self.scale = num_heads, scale
+        self.weight_v = nn.Parameter(th.empty(value_dim, hidden_dim))
+        self.weight_o = nn.Parameter(th.empty(hidden_dim, query_dim))
+        self.score_act = map_activation_str_to_layer(score_func)
+        self.score_act.dim = 2                       # the shared instance, as pred.py:292-294 sets it
+        self.g_net = nn.Linear(query_dim * 2, query_dim, bias=True)     # torch's own init draws first (RNG order)
+        init_weight(self.weight_v, init="normal")
+        init_weight(self.weight_o, init="normal")
+        nn.init.constant_(self.g_net.bias, 1.0)      # (init_weight on the g_net module itself changes nothing)
+        self.weight_q = nn.Parameter(th.empty(query_dim, hidden_dim))
+        self.weight_k = nn.Parameter(th.empty(key_dim, hidden_dim))
+        init_weight(self.weight_q, init="normal")
+        init_weight(self.weight_k, init="normal")
+
+    def forward(self, query, key, value, query_mask=None, key_mask=None):
+        from .attn import sparsemax_attention
+        q = th.matmul(query, self.weight_q)
+        k = th.matmul(key, self.weight_k)
+        v = th.matmul(value, self.weight_v)
+        a = th.matmul(sparsemax_attention(q, k, v, query_mask, key_mask, self.num_heads, self.scale), self.weight_o)
+        g = th.sigmoid(self.g_net(th.cat([query, a], dim=-1)))
+        return g * query + (1 - g) * a
+
+
+class BaseAttnPredictNet(PredictNet):
+    """pred.py:490-559: ``infer_steps`` rounds of (graph rows attend to the pattern rows, then to themselves) before the
+    ``PredictNet`` tail; the pattern side is not attended.  Padded path only (not ``poolable``)."""
+
+    def __init__(self, input_dim, hidden_dim, num_heads=1, max_seq_len=512, infer_steps=3, act_func="relu", dropout=0.0,
+                 return_weights=False):
+        super(BaseAttnPredictNet, self).__init__(input_dim, hidden_dim, act_func=act_func, dropout=dropout,
+                                                 return_weights=return_weights)
+        self.num_heads = num_heads
+        self.infer_steps = infer_steps
+        scale = 1 / (hidden_dim / num_heads) ** 0.5
+        self.p_attn = DotAttention(input_dim, input_dim, input_dim, hidden_dim, num_heads=num_heads, scale=scale)
+        self.g_attn = DotAttention(input_dim, input_dim, input_dim, hidden_dim, num_heads=num_heads, scale=scale)
+        # start near the identity: the attention prefers to pass its query through (pred.py:540-546)
+        for attn in (self.p_attn, self.g_attn):
+            for param in attn.parameters():
+                if param.requires_grad:
+                    init_weight(param, init="identity")
+
+    def infer_fn(self, g, p, g_mask, p_mask):
+        g = self.p_attn(g, p, p, query_mask=g_mask, key_mask=p_mask)
+        return self.g_attn(g, g, g, query_mask=g_mask, key_mask=g_mask)
+
+    def forward(self, p_rep, p_mask, g_rep, g_mask):
+        g = g_rep
+        for _ in range(self.infer_steps):
+            g = self.infer_fn(g, p_rep, g_mask, p_mask)
+        return super(BaseAttnPredictNet, self).forward(p_rep, p_mask, g, g_mask)
+
+
+class MeanAttnPredictNet(BaseAttnPredictNet):
+    def agg_graph(self, g_rep, g_mask=None):     # no mask: the padded length divides (pred.py:585-586)
+        return th.mean(g_rep, dim=1)
+
+
+class SumAttnPredictNet(BaseAttnPredictNet):
+    def agg_graph(self, g_rep, g_mask=None):
+        return th.sum(g_rep, dim=1)
+
+
+class MaxAttnPredictNet(BaseAttnPredictNet):
+    def agg_graph(self, g_rep, g_mask=None):     # no mask: padding rows take part (pred.py:639-640)
+        return th.max(g_rep, dim=1)[0]
+
+
+PRED_NETS = {"MeanPredictNet": MeanPredictNet, "SumPredictNet": SumPredictNet, "MaxPredictNet": MaxPredictNet,
+             "MeanAttnPredictNet": MeanAttnPredictNet, "SumAttnPredictNet": SumAttnPredictNet,
+             "MaxAttnPredictNet": MaxAttnPredictNet}
+
+
+def pred_net_kwargs(name, kw):
+    """Extra constructor arguments of a head from the model configuration: the attention heads take
+    ``pred_num_heads`` (default 4) and ``pred_infer_steps`` (default 1), as the reference's create_pred_net reads them."""
+    if issubclass(PRED_NETS[name], BaseAttnPredictNet):
+        return dict(num_heads=kw.get("pred_num_heads", 4), infer_steps=kw.get("pred_infer_steps", 1))
+    return {}

@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 84
+#define DMP_ABI_VERSION 85
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1364,6 +1364,29 @@ int dmp_gemm_k128(const float *A, int64_t lda, const float *B, int64_t ldb, int 
 /* C[E, 64] = A[E, 64] B: the same pipeline at the reference's shipped hidden_dim (two waves per workgroup). */
 int dmp_gemm_k64(const float *A, int64_t lda, const float *B, int64_t ldb, int b_transposed,
                  float *C, int64_t ldc, int64_t rows, void *stream);
+
+/* ------------------------------------------------------------------------- */
+/* Sparsemax attention (csrc/dmp_attn.hip)                                   */
+/* ------------------------------------------------------------------------- */
+/*
+ * Masked multi-head attention with sparsemax weights over the key axis, on padded batches (the core of the gated
+ * DotAttention of SubgraphCountingMatching/models/pred.py:240-487):
+ *   s_ij = scale * Q_i . K_j per head (keys with kmask 0 out),  P_i = sparsemax(s_i),  O_i = sum_j P_ij V_j
+ * Q [B, Lq, nh * dh], K / V [B, Lk, nh * dh] row-major fp32 (16-byte aligned); qmask [B, Lq], kmask [B, Lk] uint8
+ * (nonzero = live; NULL = all live; general masks, not prefixes).  dh in {4, 8, 16, 32, 64} (else
+ * DMP_ERR_UNSUPPORTED), Lk >= 1.  A row with every key masked weighs all Lk positions by 1 / Lk and sends no
+ * gradient into its scores; rows with a masked query are written as zeros (every row of every output is written).
+ * Forward state per (pair, row, head): tau [B, Lq, nh] fp32 (the threshold) and supp [B, Lq, nh] int32 (|support|,
+ * 0 = every key masked).  No [B, Lq, Lk, nh] tensor; workspaces depend on the shapes only (graph capture safe).
+ * Backward: dO -> dQ, dK, dV; delta [B, Lq, nh] fp32 is scratch (mean over the support of dO_i . V_j).
+ * No float atomics: bitwise reproducible.
+ */
+int dmp_attn_supported_dh(int dh);
+int dmp_attn_fwd(const float *Q, const float *K, const float *V, const uint8_t *qmask, const uint8_t *kmask, int64_t B, int64_t Lq,
+                 int64_t Lk, int nh, int dh, float scale, float *O, float *tau, int32_t *supp, void *stream);
+int dmp_attn_bwd(const float *Q, const float *K, const float *V, const uint8_t *qmask, const uint8_t *kmask, const float *dO,
+                 const float *tau, const int32_t *supp, int64_t B, int64_t Lq, int64_t Lk, int nh, int dh, float scale, float *delta,
+                 float *dQ, float *dK, float *dV, void *stream);
 
 #ifdef __cplusplus
 }
