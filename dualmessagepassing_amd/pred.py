@@ -1,7 +1,8 @@
 """Prediction heads of the model skeleton -- ``SubgraphCountingMatching/models/pred.py:17-233`` (``PredictNet`` and its
 Mean / Sum / Max pooling variants: dense ``[B, *]`` work after the representations have been pooled per graph) and
-pred.py:240-643 (the gated sparsemax ``DotAttention`` and the Sum / Mean / Max attention heads over the padded rows;
-the memory / DIAM heads are out of scope)."""
+pred.py:240-643 (the gated sparsemax ``DotAttention`` and the Sum / Mean / Max attention heads over the padded rows)
+and pred.py:648-1328 (``MemDotAttention``, the Sum / Mean / Max memory-attention heads and ``DIAMNet``: attention over
+``mem_len`` memory slots pooled from the padded rows by ``mem.memory_init``)."""
 import torch as th
 import torch.nn as nn
 
@@ -324,29 +325,36 @@ class MaxPredictNet(PredictNet):
 
 
 class DotAttention(nn.Module):
-    """``DotAttention`` with ``add_gate=True`` as the attention heads build it (pred.py:240-487): no dropout, no layer
-    norm, no residual, sparsemax scores over the key axis.
+    """``DotAttention`` with ``add_gate=True`` as the attention heads build it (pred.py:240-487): no dropout, no residual,
+    sparsemax scores over the key axis; ``pre_lnorm`` (the memory-attention heads) puts a LayerNorm on the query, the key
+    and the value before their projections.
 
         q, k, v = query W_q, key W_k, value W_v (split into heads);  a = sparsemax(scale q k^T) v  (query-masked rows 0)
-        a = a W_o;  g = sigmoid(g_net([query, a]));  out = g query + (1 - g) a
+        a = a W_o;  g = sigmoid(g_net([query, a]));  out = g query + (1 - g) a      (the gate sees the query as given)
 
     Parameters, their registration order and their initialisers are the reference's (``parameters()`` order
-    weight_v, weight_o, weight_q, weight_k, g_net.weight, g_net.bias).  The projections and the gate are torch GEMMs;
-    the attention core is ``attn.sparsemax_attention`` (the HIP kernels of csrc/dmp_attn.hip on the GPU)."""
+    weight_v, weight_o, weight_q, weight_k, g_net.weight, g_net.bias, then q_layer_norm, k_layer_norm, v_layer_norm with
+    ``pre_lnorm``).  The projections and the gate are torch GEMMs; the attention core is ``attn.sparsemax_attention``
+    (the HIP kernels of csrc/dmp_attn.hip on the GPU)."""
 
-    def __init__(self, query_dim, key_dim, value_dim, hidden_dim, num_heads=1, scale=1.0, score_func="sparsemax"):
+    def __init__(self, query_dim, key_dim, value_dim, hidden_dim, num_heads=1, scale=1.0, score_func="sparsemax",
+                 pre_lnorm=False):
         super(DotAttention, self).__init__()
         if hidden_dim % num_heads != 0:
             raise ValueError("Error: hidden_dim (%d) %% num_heads (%d) should be 0." % (hidden_dim, num_heads))
         if score_func != "sparsemax":
             raise NotImplementedError("DotAttention score_func=%s is outside the MI355X hot-path scope" % score_func)
         self.query_dim, self.key_dim, self.value_dim, self.hidden_dim = query_dim, key_dim, value_dim, hidden_dim
-        self.num_heads, self.scale = num_heads, scale
+        self.num_heads, self.scale, self.pre_lnorm = num_heads, scale, pre_lnorm
         self.weight_v = nn.Parameter(th.empty(value_dim, hidden_dim))
         self.weight_o = nn.Parameter(th.empty(hidden_dim, query_dim))
         self.score_act = map_activation_str_to_layer(score_func)
         self.score_act.dim = 2                       # the shared instance, as pred.py:292-294 sets it
         self.g_net = nn.Linear(query_dim * 2, query_dim, bias=True)     # torch's own init draws first (RNG order)
+        if pre_lnorm:                                # default affine init (init_weight on a module changes nothing)
+            self.q_layer_norm = nn.LayerNorm(query_dim)
+            self.k_layer_norm = nn.LayerNorm(key_dim)
+            self.v_layer_norm = nn.LayerNorm(value_dim)
         init_weight(self.weight_v, init="normal")
         init_weight(self.weight_o, init="normal")
         nn.init.constant_(self.g_net.bias, 1.0)      # (init_weight on the g_net module itself changes nothing)
@@ -357,12 +365,15 @@ class DotAttention(nn.Module):
 
     def forward(self, query, key, value, query_mask=None, key_mask=None):
         from .attn import sparsemax_attention
+        original_query = query
+        if self.pre_lnorm:
+            query, key, value = self.q_layer_norm(query), self.k_layer_norm(key), self.v_layer_norm(value)
         q = th.matmul(query, self.weight_q)
         k = th.matmul(key, self.weight_k)
         v = th.matmul(value, self.weight_v)
         a = th.matmul(sparsemax_attention(q, k, v, query_mask, key_mask, self.num_heads, self.scale), self.weight_o)
-        g = th.sigmoid(self.g_net(th.cat([query, a], dim=-1)))
-        return g * query + (1 - g) * a
+        g = th.sigmoid(self.g_net(th.cat([original_query, a], dim=-1)))
+        return g * original_query + (1 - g) * a
 
 
 class BaseAttnPredictNet(PredictNet):
@@ -410,14 +421,167 @@ class MaxAttnPredictNet(BaseAttnPredictNet):
         return th.max(g_rep, dim=1)[0]
 
 
+class MemDotAttention(DotAttention):
+    """pred.py:777-869: the keys and the values are projected (``proj_k``, ``proj_v``: key_dim / value_dim -> mem_dim),
+    pooled into ``mem_len`` memory slots per pair (``mem.memory_init``: one HIP launch for both on the GPU), and attended
+    with the memory mask as the key mask.  The memory-attention heads use ``pre_lnorm``."""
+
+    def __init__(self, query_dim, key_dim, value_dim, mem_dim, hidden_dim, num_heads=1, scale=1.0, mem_len=1, mem_init="mean",
+                 score_func="sparsemax", pre_lnorm=False):
+        from .mem import parse_mem_init
+        parse_mem_init(mem_init)
+        super(MemDotAttention, self).__init__(query_dim, mem_dim, mem_dim, hidden_dim, num_heads=num_heads, scale=scale,
+                                              score_func=score_func, pre_lnorm=pre_lnorm)
+        self.mem_len, self.mem_init = mem_len, mem_init
+        self.proj_k = nn.Linear(key_dim, mem_dim)    # torch's own init (the reference's init_weight(module) changes nothing)
+        self.proj_v = nn.Linear(value_dim, mem_dim)
+
+    def init_memory(self, k, v, key_mask):
+        """The key and the value memory of the projected rows and their shared memory mask (pred.py:842-866: the slice
+        of every pair ends at its last live position, which it drops)."""
+        from .mem import memory_init
+        (mk, mv), mmask = memory_init([k, v], key_mask, self.mem_len, self.mem_init, inclusive_end=False)
+        return mk, mv, mmask
+
+    def forward(self, query, key, value, query_mask=None, key_mask=None):
+        mk, mv, mmask = self.init_memory(self.proj_k(key), self.proj_v(value), key_mask)
+        return super(MemDotAttention, self).forward(query, mk, mv, query_mask, mmask)
+
+
+class BaseMemAttnPredictNet(BaseAttnPredictNet):
+    """pred.py:872-972: ``BaseAttnPredictNet`` with ``MemDotAttention`` for both attentions: the graph rows attend to
+    ``mem_len`` slots pooled from the pattern rows, then to ``mem_len`` slots pooled from themselves.  Scale 1,
+    ``pre_lnorm``, identity init over every parameter that requires a gradient (LayerNorms and projections included).
+    ``mem_init`` is a class default of each subclass (the reference's create_pred_net does not pass it)."""
+
+    mem_init_default = "mean"
+
+    def __init__(self, input_dim, hidden_dim, num_heads=1, max_seq_len=512, infer_steps=3, mem_len=4, mem_init=None,
+                 act_func="relu", dropout=0.0, return_weights=False):
+        # the PredictNet tail directly: BaseAttnPredictNet.__init__ would build plain DotAttentions (and draw their RNG)
+        PredictNet.__init__(self, input_dim, hidden_dim, act_func=act_func, dropout=dropout, return_weights=return_weights)
+        self.mem_len = mem_len
+        self.mem_init = self.mem_init_default if mem_init is None else mem_init
+        self.num_heads = num_heads
+        self.infer_steps = infer_steps
+        for name in ("p_attn", "g_attn"):
+            setattr(self, name, MemDotAttention(input_dim, input_dim, input_dim, hidden_dim, hidden_dim, num_heads=num_heads,
+                                                scale=1.0, mem_len=mem_len, mem_init=self.mem_init, pre_lnorm=True))
+        for attn in (self.p_attn, self.g_attn):      # pred.py:944-950
+            for param in attn.parameters():
+                if param.requires_grad:
+                    init_weight(param, init="identity")
+
+
+class MeanMemAttnPredictNet(BaseMemAttnPredictNet):
+    mem_init_default = "mean"
+
+    def agg_graph(self, g_rep, g_mask=None):
+        return th.mean(g_rep, dim=1)
+
+
+class SumMemAttnPredictNet(BaseMemAttnPredictNet):
+    mem_init_default = "sum"
+
+    def agg_graph(self, g_rep, g_mask=None):
+        return th.sum(g_rep, dim=1)
+
+
+class MaxMemAttnPredictNet(BaseMemAttnPredictNet):
+    mem_init_default = "max"
+
+    def agg_graph(self, g_rep, g_mask=None):
+        return th.max(g_rep, dim=1)[0]
+
+
+class DIAMNet(PredictNet):
+    """pred.py:1043-1328, the head of "Neural Subgraph Isomorphism Counting" (Liu et al.): the target rows are pooled into
+    ``mem_len`` slots (``mem.memory_init`` with the slice ending after the last live position, then ``mem_layer``), the
+    memory attends to the pattern rows and to the target rows ``infer_steps`` times, and the count reads the flattened
+    memory.  With ``return_weights`` the pattern and target rows attend to the memory (``m_attn``) for the matching
+    weights; the reference's forward only runs that path with ``mem_len == 4`` (its new ``weight_fc1`` is
+    ``mem_dim * mem_len + 2`` wide but is fed ``4 * hidden_dim + 2`` features), so other lengths are refused here.
+
+    Sub-modules, registration order and initialisation are the reference's: ``mem_layer``, ``p_attn``, ``g_attn``,
+    ``m_attn``, then the replaced ``weight_fc1`` and ``pred_fc1`` (torch's own init: the reference's
+    ``init_weight(module)`` calls on them change nothing), then identity init over the three attentions."""
+
+    def __init__(self, input_dim, hidden_dim, act_func="relu", num_heads=1, max_seq_len=512, infer_steps=1, mem_len=4,
+                 mem_init="mean", dropout=0.0, return_weights=False):
+        from .mem import parse_mem_init
+        parse_mem_init(mem_init)
+        if return_weights and mem_len != 4:
+            raise ValueError("DIAMNet with return_weights needs mem_len == 4 (got %d): the reference's weight_fc1 takes "
+                             "mem_dim * mem_len + 2 inputs but its forward feeds it 4 * hidden_dim + 2" % mem_len)
+        super(DIAMNet, self).__init__(input_dim, hidden_dim, act_func=act_func, dropout=dropout, return_weights=return_weights)
+        self.num_heads, self.infer_steps, self.mem_len, self.mem_init = num_heads, infer_steps, mem_len, mem_init
+        mem_dim = hidden_dim
+        self.mem_layer = nn.Linear(input_dim, mem_dim)
+        scale = 1 / (hidden_dim / num_heads) ** 0.5
+        self.p_attn = DotAttention(mem_dim, input_dim, input_dim, hidden_dim, num_heads=num_heads, scale=scale)
+        self.g_attn = DotAttention(mem_dim, input_dim, input_dim, hidden_dim, num_heads=num_heads, scale=scale)
+        self.m_attn = DotAttention(hidden_dim, mem_dim, mem_dim, hidden_dim, num_heads=num_heads, scale=scale)
+        if return_weights:
+            del self.weight_fc1
+            self.weight_fc1 = nn.Linear(mem_dim * mem_len + 2, hidden_dim)
+        del self.pred_fc1
+        self.pred_fc1 = nn.Linear(mem_dim * mem_len + 4, hidden_dim)
+        init_weight(self.pred_fc1, activation=act_func, init="normal")     # a module: no-op, as in the reference
+        if return_weights:
+            init_weight(self.weight_fc1, activation=act_func, init="normal")
+        for attn in (self.p_attn, self.g_attn, self.m_attn):
+            for param in attn.parameters():
+                if param.requires_grad:
+                    init_weight(param, init="identity")
+
+    def agg_pattern(self, p_rep, p_mask=None):
+        if self.mem_init.endswith("max"):
+            return th.max(p_rep, dim=1)[0]
+        if self.mem_init.endswith("sum"):
+            return th.sum(p_rep, dim=1)
+        return th.mean(p_rep, dim=1)
+
+    def init_memory(self, x, x_mask):
+        from .mem import memory_init
+        (m,), mmask = memory_init([x], x_mask, self.mem_len, self.mem_init, inclusive_end=True)
+        return self.mem_layer(m), mmask
+
+    def infer_fn(self, m, p, g, m_mask, p_mask, g_mask):
+        m = self.p_attn(m, p, p, query_mask=m_mask, key_mask=p_mask)
+        return self.g_attn(m, g, g, query_mask=m_mask, key_mask=g_mask)
+
+    def forward(self, p_rep, p_mask, g_rep, g_mask):
+        sizes = self._size_features(p_mask, g_mask)
+        m, m_mask = self.init_memory(g_rep, g_mask)
+        for _ in range(self.infer_steps):
+            m = self.infer_fn(m, p_rep, g_rep, m_mask, p_mask, g_mask)
+        w = None
+        if self.weight_fc1 is not None:
+            p = self.agg_pattern(self.drop(self.m_attn(self.p_fc(p_rep), m, m, p_mask, m_mask)), p_mask)
+            g = self.drop(self.m_attn(self.g_fc(g_rep), m, m, g_mask, m_mask))
+            w = self._row_weights(p, g, sizes)
+        y = th.cat([m.reshape(m.size(0), -1), sizes], dim=1)
+        y = self.pred_fc2(th.cat([self.act(self.pred_fc1(y)), sizes], dim=1))
+        return y, w
+
+
 PRED_NETS = {"MeanPredictNet": MeanPredictNet, "SumPredictNet": SumPredictNet, "MaxPredictNet": MaxPredictNet,
              "MeanAttnPredictNet": MeanAttnPredictNet, "SumAttnPredictNet": SumAttnPredictNet,
-             "MaxAttnPredictNet": MaxAttnPredictNet}
+             "MaxAttnPredictNet": MaxAttnPredictNet, "MeanMemAttnPredictNet": MeanMemAttnPredictNet,
+             "SumMemAttnPredictNet": SumMemAttnPredictNet, "MaxMemAttnPredictNet": MaxMemAttnPredictNet, "DIAMNet": DIAMNet}
 
 
 def pred_net_kwargs(name, kw):
-    """Extra constructor arguments of a head from the model configuration: the attention heads take
-    ``pred_num_heads`` (default 4) and ``pred_infer_steps`` (default 1), as the reference's create_pred_net reads them."""
-    if issubclass(PRED_NETS[name], BaseAttnPredictNet):
+    """Extra constructor arguments of a head from the model configuration, as the reference's create_pred_net reads them:
+    the attention heads take ``pred_num_heads`` (default 4) and ``pred_infer_steps`` (default 1); the memory heads also
+    ``pred_mem_len`` (default 4), and DIAMNet ``pred_mem_init`` (default "mean")."""
+    cls = PRED_NETS[name]
+    if issubclass(cls, (BaseMemAttnPredictNet, DIAMNet)):
+        out = dict(num_heads=kw.get("pred_num_heads", 4), infer_steps=kw.get("pred_infer_steps", 1),
+                   mem_len=kw.get("pred_mem_len", 4))
+        if cls is DIAMNet:
+            out["mem_init"] = kw.get("pred_mem_init", "mean")
+        return out
+    if issubclass(cls, BaseAttnPredictNet):
         return dict(num_heads=kw.get("pred_num_heads", 4), infer_steps=kw.get("pred_infer_steps", 1))
     return {}

@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 85
+#define DMP_ABI_VERSION 86
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1387,6 +1387,36 @@ int dmp_attn_fwd(const float *Q, const float *K, const float *V, const uint8_t *
 int dmp_attn_bwd(const float *Q, const float *K, const float *V, const uint8_t *qmask, const uint8_t *kmask, const float *dO,
                  const float *tau, const int32_t *supp, int64_t B, int64_t Lq, int64_t Lk, int nh, int dh, float scale, float *delta,
                  float *dQ, float *dK, float *dV, void *stream);
+
+/* ------------------------------------------------------------------------- */
+/* Memory initialisation of the memory-attention heads (csrc/dmp_mem.hip)    */
+/* ------------------------------------------------------------------------- */
+/*
+ * Pools every pair's padded rows into M memory slots (init_mem of SubgraphCountingMatching/models/pred.py:648-775, as
+ * MemDotAttention.init_memory and DIAMNet.init_memory call it per pair).  Per pair b, from mask [B, L] uint8 (nonzero = live):
+ *   s = first live position, e = last live position (both 0 when no position is live);
+ *   n = e - s (inclusive_end 0: the memory-attention heads, the reference's slice drops the last live row) or e - s + 1
+ *   (inclusive_end 1: DIAMNet);  the segment is rows s .. s+n-1 as they are (masked interior rows included);
+ *   circular 1: extended row p = segment row p mod n for p < n' = n + ceil((n+1)/2) - 1;  circular 0: n' = n;
+ *   n' <= M: slots 0 .. M-n'-1 are zero with mask 0, slot M-n'+q is extended row q with its mask bit;
+ *   n' >  M: stride = n' / M, k = n' - (M-1) stride; slot i = mean / sum / max of extended rows i stride .. i stride + k - 1
+ *            (per element; windows overlap when k > stride), its mask = OR of their mask bits.
+ * X0 (and X1, or NULL) fp32 rows: row (b, l) at X + (b L + l) ldx, ldx >= D, ldx % 4 == 0, 16-byte aligned, D % 4 == 0.
+ * X1 is pooled with the same windows (the key and the value memory of one attention).  Outputs: Y0 / Y1 [B, M, D] fp32,
+ * ymask [B, M] uint8 (0 / 1), seg [B, 2] int32 (s, n: the backward's input), and for DMP_MEM_MAX arg0 / arg1 [B, M, D] int32:
+ * the extended position of the first maximum of every element (-1 in an empty slot).  Every output element is written;
+ * s and e are found on the device (no host read; nothing depends on the data but the values).
+ * Backward: dX0 / dX1 [B, L, D] contiguous, every element written (rows outside the segment 0); gather form (a row covered at
+ * p and p + n, or by two windows, sums its shares in a fixed order), no float atomics: bitwise reproducible.
+ */
+#define DMP_MEM_MEAN 0
+#define DMP_MEM_SUM 1
+#define DMP_MEM_MAX 2
+int dmp_mem_init_fwd(const float *X0, int64_t ldx0, const float *X1, int64_t ldx1, const uint8_t *mask, int64_t B, int64_t L, int D,
+                     int M, int mode, int circular, int inclusive_end, float *Y0, float *Y1, uint8_t *ymask, int32_t *arg0,
+                     int32_t *arg1, int32_t *seg, void *stream);
+int dmp_mem_init_bwd(const float *dY0, const float *dY1, const int32_t *arg0, const int32_t *arg1, const int32_t *seg, int64_t B,
+                     int64_t L, int D, int M, int mode, int circular, float *dX0, float *dX1, void *stream);
 
 #ifdef __cplusplus
 }
