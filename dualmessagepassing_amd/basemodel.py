@@ -1108,4 +1108,7 @@ def build_model(config=None, **kw):
     if rep_net in ("LRP", "DMPLRP"):
         from . import lrp
         return getattr(lrp, rep_net)(**config)
+    if rep_net == "CNN":
+        from .seqmodel import CNN
+        return CNN(**config)
     raise NotImplementedError("rep_net=%s is outside the MI355X hot-path scope" % rep_net)

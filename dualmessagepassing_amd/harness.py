@@ -195,6 +195,12 @@ class PairDataset:
                                      torch.from_numpy(ptr_host).to(device), return_weights, work_hint=int(hint))
         return out[0], out[1], counts, weights
 
+    def edge_seq(self):
+        """The edge-sequence view of this dataset (``EdgeSeqPairs``): what the sequence rep-nets (CNN) train on."""
+        if getattr(self, "_edge_seq", None) is None:
+            self._edge_seq = EdgeSeqPairs(self)
+        return self._edge_seq
+
     ARRAYS_PER_GRAPH = 9    # src, dst, num_nodes, num_edges, node id, node label, edge id, edge label, is_reversed
 
     def pad_buckets(self, batch_size, levels=4):
@@ -292,6 +298,46 @@ class PairDataset:
                              ndata={"id": nid, "label": vlabel}, edata={"id": eid, "label": elabel, "is_reversed": rev},
                              max_nodes=max_n, max_edges=max_e))
         return collate_device_many(jobs)                         # both sides in one pair of launches
+
+
+class EdgeSeqPairs:
+    """A ``PairDataset`` as the reference's ``EdgeSeqDataset`` after ``add_reversed_edges`` (dataset.py:885-1052,
+    train.py:273-297): every pattern and graph a sorted tuple sequence with its reversed tuples merged in, and the per-tuple
+    subisomorphism edge weights, prepared once here on the host.  ``batchify`` has ``PairDataset.batchify``'s signature and
+    returns ``(EdgeSeq pattern, EdgeSeq graph, counts [B, 1], (None, edge_weights [B, L] or None))``: one upload and
+    index ops per batch (``EdgeSeq.batch``)."""
+
+    def __init__(self, pairs):
+        from . import edgeseq
+        self.samples, self.shape = pairs.samples, pairs.shape
+        nel = int(self.shape["n_elabels"])
+        self.seqs = []
+        for x in self.samples:
+            item = {}
+            for key in ("pattern", "graph"):
+                g = x[key]
+                e = len(g["src"]) // 2                            # the stored form: [forward | reversed] edges
+                fwd = edgeseq.from_graph(g["src"][:e], g["dst"][:e], np.arange(g["num_nodes"]), g["vlabel"], g["elabel"][:e])
+                code, flag, _ = edgeseq.add_reversed_edges(fwd, nel)
+                item[key] = (fwd, code, flag)
+            w = edgeseq.edge_weights(item["pattern"][0], item["graph"][0], x["subisomorphisms"], int(x["counts"]))
+            item["edge_weights"] = edgeseq.map_reversed_weights(item["graph"][1], item["graph"][2], w, nel)
+            self.seqs.append(item)
+
+    def __len__(self):
+        return len(self.samples)
+
+    def batchify(self, indices, device, return_weights=None):
+        from .edgeseq import EdgeSeq
+        items = [self.seqs[i] for i in indices]
+        if isinstance(return_weights, str):
+            return_weights = return_weights.split(",")
+        want = bool(return_weights) and "edge" in return_weights
+        pattern, _ = EdgeSeq.batch([x["pattern"][1] for x in items], device, flags=[x["pattern"][2] for x in items])
+        graph, extra = EdgeSeq.batch([x["graph"][1] for x in items], device, flags=[x["graph"][2] for x in items],
+                                     extra=[[x["edge_weights"] for x in items]] if want else None)
+        counts = torch.tensor([self.samples[i]["counts"] for i in indices], dtype=torch.float32, device=device).unsqueeze(-1)
+        return pattern, graph, counts, (None, extra[0] if want else None)
 
 
 class SyntheticPairs(PairDataset):
@@ -550,6 +596,9 @@ def train_epoch(model, optimizer, dataset, batch_size, device, sync=None, bp_los
         loss = count_loss(pred, counts, bp_loss, neg_slp) if pred.shape == counts.shape else _CRIT[bp_loss](F.leaky_relu(pred, neg_slp), counts)
         for w, pk, mk in ((node_w, "pred_v", "g_v_mask"), (edge_w, "pred_e", "g_e_mask")):
             if w is not None and out[pk] is not None:
+                if pk == "pred_e":      # train.py:636-641 (the graph models' refine_edge_weights is the identity)
+                    with torch.no_grad():
+                        w = model.refine_edge_weights(w.float())
                 m_loss, m_reg = _match_terms(_CRIT[bp_loss], out[pk], w, out[mk], pred, neg_slp)
                 loss = loss + match_loss_w * m_loss + match_reg_w * m_reg
         if rep_reg_w > 0:  # train.py:651-659 (bp_crit with slope 1: the plain criterion against zeros)
@@ -594,6 +643,10 @@ class GraphedTrainStep:
         Not with the representation regulariser (it reads every row) or BatchNorm layers (their statistics would see the
         inert rows): such runs keep the exact shapes."""
         from .dp import StepGraph
+        from .seqmodel import EdgeSeqModel
+        if isinstance(model, EdgeSeqModel):
+            raise ValueError("GraphedTrainStep records the graph models' steps only: %s (an edge-sequence model) trains "
+                             "eagerly (train_epoch without graph=...)" % type(model).__name__)
         if getattr(sync, "world", 1) != 1:
             raise ValueError("GraphedTrainStep records single-rank steps only")
         if not getattr(optimizer, "capturable", False):

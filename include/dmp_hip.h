@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 86
+#define DMP_ABI_VERSION 87
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1417,6 +1417,26 @@ int dmp_mem_init_fwd(const float *X0, int64_t ldx0, const float *X1, int64_t ldx
                      int32_t *arg1, int32_t *seg, void *stream);
 int dmp_mem_init_bwd(const float *dY0, const float *dY1, const int32_t *arg0, const int32_t *arg1, const int32_t *seg, int64_t B,
                      int64_t L, int D, int M, int mode, int circular, float *dX0, float *dX1, void *stream);
+
+/* ---- CNN rep-net layer of the edge-sequence models (dmp_cnn.hip): channels-last rows X [B, L, H], H in {64, 128},
+ * stride 1, dilation 1, conv kernel k <= 8 with padding pad < k, max-pool kernel pk <= k with padding pp, 2 pp <= pk.
+ * Lc = L + 2 pad - k + 1, Lout = Lc + 2 pp - pk + 1.  Wt [k, H_in, H_out]: Wt[j][i][o] = W[o, i, j].
+ * Y [B, Lout, H] = pool(act(conv(X) + bias)) (* the gate after the layer if gate_in and apply_gate) (+ resid [B, Lout, H]);
+ * act 0: identity, 1: max(x, slope x).  arg (optional) [B, Lout, H] uint8: offset of the window's first maximum | 0x80 if
+ * that maximum is > 0.  gate_out [B, Lout] (required with gate_in [B, L]): max of gate_in over the conv, then the pool
+ * windows.  pk = 1, pp = 0, act 0: a plain conv (the transposed conv of the backward). */
+int dmp_cnn_fwd(const float *X, int64_t B, int64_t L, int H, const float *Wt, const float *bias, int k, int pad, int pk, int pp,
+                int act, float slope, const float *gate_in, int apply_gate, const float *resid, float *Y, uint8_t *arg,
+                float *gate_out, void *stream);
+/* dC [B, Lc, H] = the gradient at the conv output (before the activation) from dY [B, Lout, H] at the pool output: each pool
+ * row's dY (* gate [B, Lout] if given) to its window's maximum, times the activation's slope there.  Gather form. */
+int dmp_cnn_route_bwd(const float *dY, const float *gate, const uint8_t *arg, int64_t B, int64_t Lc, int64_t Lout, int H, int pk,
+                      int pp, float slope, float *dC, void *stream);
+/* Number of row chunks of dmp_cnn_wgrad for B * Lc rows. */
+int64_t dmp_cnn_wgrad_chunks(int64_t rows);
+/* partial [chunks, k H H + H]: per chunk of (b, s) rows, dW as [k][o][i] and db [H]; sum them with dmp_reduce_partials. */
+int dmp_cnn_wgrad(const float *dC, const float *X, int64_t B, int64_t L, int64_t Lc, int H, int k, int pad, float *partial,
+                  void *stream);
 
 #ifdef __cplusplus
 }
