@@ -176,6 +176,15 @@ def init_module(x, activation="none", init="uniform"):
                 _EMBEDDING_INITS[init](x.weight)
             if x.padding_idx is not None:
                 x.weight[x.padding_idx].fill_(0)
+    elif isinstance(x, nn.RNNBase):
+        # utils/init.py:184-190: every weight by ``init`` at gain 1 (not the activation's), every bias zero, in
+        # ``_all_weights`` order (the RNG order of the reference)
+        for layer_weights in x._all_weights:
+            for w in layer_weights:
+                if "weight" in w:
+                    _INITS[init](getattr(x, w), 1.0)
+                elif "bias" in w:
+                    nn.init.zeros_(getattr(x, w))
     elif isinstance(x, _NORMS):
         nn.init.ones_(x.weight)
         nn.init.zeros_(x.bias)

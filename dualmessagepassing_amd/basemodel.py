@@ -1111,4 +1111,7 @@ def build_model(config=None, **kw):
     if rep_net == "CNN":
         from .seqmodel import CNN
         return CNN(**config)
+    if rep_net == "RNN":
+        from .seqmodel import RNN
+        return RNN(**config)
     raise NotImplementedError("rep_net=%s is outside the MI355X hot-path scope" % rep_net)

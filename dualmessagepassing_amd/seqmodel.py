@@ -1,10 +1,12 @@
-"""The edge-sequence models: ``EdgeSeqModel`` (``SubgraphCountingMatching/models/basemodel.py:222-617``) and its first
-rep-net, ``CNN`` (``models/cnn.py``).
+"""The edge-sequence models: ``EdgeSeqModel`` (``SubgraphCountingMatching/models/basemodel.py:222-617``) and its
+rep-nets ``CNN`` (``models/cnn.py``) and ``RNN`` (``models/rnn.py``).
 
 Same constructor keywords, sub-module names (hence ``state_dict`` keys), initialisers and seeded RNG order as the
 reference, and ``forward(pattern, graph) -> OutputDict`` with its 15 keys (the ``*_v_*`` entries None).  The inputs are
-``edgeseq.EdgeSeq`` batches.  Activations stay channels-last ``[B, L, H]``: a layer runs either the fused HIP kernels of
-``cnn.py`` (``cnn.hip_layer_ok``) or the reference's tensor ops on a transposed view; both compute the same function."""
+``edgeseq.EdgeSeq`` batches.  Activations stay channels-last ``[B, L, H]``: a CNN layer runs either the fused HIP kernels
+of ``cnn.py`` (``cnn.hip_layer_ok``) or the reference's tensor ops on a transposed view, an RNN layer either the recurrence
+kernels of ``rnn.py`` (``rnn.hip_layer_ok``) or its own ``nn.LSTM`` / ``nn.GRU`` / ``nn.RNN``; both compute the same
+function."""
 from collections import OrderedDict
 
 import torch as th
@@ -12,6 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import cnn as _cnn
+from . import rnn as _rnn
 from ._lib import on_input_device
 from .act import init_module, map_activation_str_to_layer
 from .basemodel import BaseModel, OutputDict, ScalarFilter
@@ -311,4 +314,84 @@ class CNN(EdgeSeqModel):
         return weights.to(dtype)
 
 
-SEQ_MODELS = {"CNN": CNN}
+class RNNLayer(nn.Module):
+    """rnn.py:13-52: a one-layer ``nn.LSTM`` / ``nn.GRU`` / ``nn.RNN`` (tanh), batch first, hidden ``hid_dim // 2`` per
+    direction when bidirectional, then dropout.  The reference's ``layer_norm`` argument is kept, but its ``RNN`` never
+    passes it.  The model calls ``forward_rows`` with the gate and the residual."""
+
+    def __init__(self, rep_rnn_type, input_dim, hid_dim, layer_norm=False, bidirectional=False, dropout=0.0):
+        super(RNNLayer, self).__init__()
+        self.input_dim = input_dim
+        self.hid_dim = hid_dim
+        cls = {"LSTM": nn.LSTM, "GRU": nn.GRU, "RNN": nn.RNN}.get(rep_rnn_type)
+        if cls is None:
+            raise ValueError("rep_rnn_type=%s is not supported (LSTM, GRU or RNN)" % (rep_rnn_type,))
+        self.rnn_type = rep_rnn_type
+        self.layer = cls(input_dim, hid_dim // 2 if bidirectional else hid_dim, bidirectional=bidirectional, batch_first=True)
+        self.ln = nn.LayerNorm(hid_dim) if layer_norm else None
+        self.drop = nn.Dropout(dropout)
+        init_module(self.layer)
+
+    def forward(self, x):
+        o = self.layer(x)[0]
+        if self.ln is not None:
+            o = self.ln(o)
+        return self.drop(o)
+
+    def get_output_dim(self):
+        return self.hid_dim - self.hid_dim % 2
+
+    def forward_rows(self, x, gate, residual):
+        """x [B, L, H], gate [B, L] float or None -> ``layer(x) * gate (+ x when residual and the sizes match)``.  The
+        recurrence runs over all L positions, the padding included, as the reference's does."""
+        if _rnn.hip_layer_ok(self, x, gate):
+            return _rnn.rnn_layer_hip(self, x, gate, residual)
+        o = self(x)
+        if gate is not None:
+            o = o * gate.unsqueeze(-1)
+        if residual and o.size() == x.size():
+            o = x + o
+        return o
+
+
+class RNN(EdgeSeqModel):
+    """rnn.py:55-124."""
+
+    def create_rep_net(self, type, **kw):
+        if type == "graph":
+            num_layers = kw.get("rep_num_graph_layers", 1)
+        elif type == "pattern":
+            if self.share_rep_net:
+                return self.g_rep_net
+            num_layers = kw.get("rep_num_pattern_layers", 1)
+        else:
+            raise ValueError(type)
+        rep_rnn_type = kw.get("rep_rnn_type", "LSTM")
+        bidirectional = kw.get("rep_rnn_bidirectional", False)
+        dropout = kw.get("rep_dropout", 0.0)
+        rnn = nn.ModuleList()
+        for i in range(num_layers):
+            rnn.add_module("%s_rnn_(%d)" % (type, i),
+                           RNNLayer(rep_rnn_type, self.hid_dim, self.hid_dim, bidirectional=bidirectional, dropout=dropout))
+        return nn.ModuleDict({"rnn": rnn})
+
+    def _rep(self, net, x, gate, residual):
+        for layer in net["rnn"]:
+            x = layer.forward_rows(x, gate, residual)
+        return x
+
+    def get_pattern_rep(self, p_emb, mask=None):
+        # with a mask (forward always passes one): masked input, every layer's output masked, no residual
+        if mask is None:
+            return self._rep(self.p_rep_net, p_emb, None, self.rep_residual)
+        m = mask.float().view(mask.size(0), -1)
+        return self._rep(self.p_rep_net, p_emb.masked_fill(~mask, 0.0), m, False)
+
+    def get_graph_rep(self, g_emb, mask=None, gate=None):
+        if mask is None and gate is None:
+            return self._rep(self.g_rep_net, g_emb, None, self.rep_residual)
+        g = (mask.float() if mask is not None else 1) * (gate if gate is not None else 1)
+        return self._rep(self.g_rep_net, g_emb * g, g.view(g_emb.size(0), -1), self.rep_residual)
+
+
+SEQ_MODELS = {"CNN": CNN, "RNN": RNN}

@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 87
+#define DMP_ABI_VERSION 88
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1437,6 +1437,20 @@ int64_t dmp_cnn_wgrad_chunks(int64_t rows);
 /* partial [chunks, k H H + H]: per chunk of (b, s) rows, dW as [k][o][i] and db [H]; sum them with dmp_reduce_partials. */
 int dmp_cnn_wgrad(const float *dC, const float *X, int64_t B, int64_t L, int64_t Lc, int H, int k, int pad, float *partial,
                   void *stream);
+
+/* ---- RNN rep-net layer of the edge-sequence models (dmp_rnn.hip): the time recurrence of a one-layer nn.LSTM (cell 0),
+ * nn.GRU (cell 1) or nn.RNN with tanh (cell 2), D = 1 or 2 directions (direction 1 runs from position L - 1 down), Hd in
+ * {32, 64, 128} units per direction, G gates (4, 3, 1).  One launch runs all L steps; workgroups hold kS = 4 sequences each.
+ * P [B, L, D, G Hd]: X W_ihᵀ + b (LSTM / RNN b = b_ih + b_hh; GRU: b_ih, with b_hh for r and z only).  Whh [D, G Hd, Hd]
+ * (16-byte aligned), bhn [D, Hd] (GRU's b_hn; NULL otherwise).  gate [B, L] and resid [B, L, D Hd] optional.
+ * Y [B, L, D Hd] = h * gate + resid; H [B, L, D Hd] = h; S [B, L, D, NS Hd] the cell values for the backward (LSTM NS 5:
+ * i f g o c; GRU 4: r z n, W_hn h + b_hn; RNN: none, S may be NULL). */
+int dmp_rnn_fwd(const float *P, const float *Whh, const float *bhn, const float *gate, const float *resid, int64_t B, int64_t L,
+                int D, int Hd, int cell, float *Y, float *H, float *S, void *stream);
+/* The reverse-time recurrence: dG [B, L, D, NG Hd], the gradients before the activations (LSTM NG 4: i f g o; GRU 4:
+ * r z n and W_hn h + b_hn; RNN 1) from dY [B, L, D Hd] at Y (times gate if given) and the forward's H and S. */
+int dmp_rnn_bwd(const float *dY, const float *gate, const float *Whh, const float *H, const float *S, int64_t B, int64_t L, int D,
+                int Hd, int cell, float *dG, void *stream);
 
 #ifdef __cplusplus
 }
