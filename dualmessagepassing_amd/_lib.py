@@ -152,7 +152,6 @@ SIGNATURES = {
     "dmp_pool_relu_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64,
                                   c_ptr, c_ptr, c_ptr]),
     "dmp_relu_bwd_gathered_colsum": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_dev_set_mfma_variant": (None, [c_int]),
     "dmp_dev_set_exact_fp32": (None, [c_int]),
     "dmp_dev_get_exact_fp32": (c_int, []),
     "dmp_rel_gemm": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64,
@@ -162,7 +161,7 @@ SIGNATURES = {
     "dmp_atb_typed_blocks_h": (c_i64, [c_i64, c_int]),
     "dmp_atb_rows_blocks_h": (c_i64, [c_i64, c_int, c_int, c_int]),
     "dmp_atb_rows_plain": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "dmp_atb_rows_masked": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "dmp_atb_rows_masked": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
     "dmp_atb_jobs_blocks_h": (c_i64, [c_i64, c_int, c_int]),
     "dmp_atb_rows_jobs_h": (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     "dmp_atb_tile_jobs_blocks": (c_i64, [c_i64, c_int, c_int]),
@@ -222,7 +221,7 @@ SIGNATURES = {
     "dmp_rnn_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr]),
 }
 
-ABI_VERSION = 88
+ABI_VERSION = 89
 # ``_lib.VALIDATE = True``: index builds read back the kernels' status word (one host sync each) and raise on an edge endpoint
 # or a lookup index outside its range -- otherwise such an entry is dropped from the CSR and gathers read row 0 (validate
 # datasets once with harness.validate_samples, or run a debugging pass with this attribute set)

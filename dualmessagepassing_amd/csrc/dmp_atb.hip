@@ -44,7 +44,6 @@ struct AtbArgs {
   const float *slot_scale;         // relational variant: [tiles * 32] scale of Z's row per slot, or NULL
   const int32_t *type_tile_ptr;    // relational variant: [types + 1] first tile of every type
   const uint32_t *rowmask;         // rows variant with a gate: bit r of rowmask[t] == 0 -> row 32 t + r has gate 0 and is not fetched
-  int rows_x6;                     // rows variant: 1 = on the bf16 pipe (dmp_atb_rows_masked picks it)
 };
 
 enum { ATB_ROWS = 0, ATB_TYPED = 1, ATB_REL = 2, ATB_PLAIN = 3 };   // PLAIN: the rows variant without a gate and without column sums (compile time: the gated form
@@ -411,8 +410,9 @@ inline bool opt_in_lds(const void *kernel, int bytes, bool (&done)[kMaxDevices])
 template <int MODE, int H = 128>
 bool lds_ready() {
   static bool done[kMaxDevices] = {}, done_exact[kMaxDevices] = {}, done_big[kMaxDevices] = {};
-  return opt_in_lds(reinterpret_cast<const void *>(&atb_k<MODE, H, true>), atb_lds_bytes(H), done) &&
-         opt_in_lds(reinterpret_cast<const void *>(&atb_k<MODE, H, false>), atb_lds_bytes(H), done_exact) &&
+  if constexpr (MODE != ATB_ROWS)          // (the gated rows variant has no bf16x6 form: see launch_atb)
+    if (!opt_in_lds(reinterpret_cast<const void *>(&atb_k<MODE, H, true>), atb_lds_bytes(H), done)) return false;
+  return opt_in_lds(reinterpret_cast<const void *>(&atb_k<MODE, H, false>), atb_lds_bytes(H), done_exact) &&
          opt_in_lds(reinterpret_cast<const void *>(&atb_k<MODE, H, MODE == ATB_TYPED, true>), atb_lds_bytes(H), done_big);
 }
 // The bf16x6 form is used where it was measured faster: the class-typed product (its rows are gathered, the f32 form's
@@ -425,9 +425,13 @@ void launch_atb(const AtbArgs &a, dim3 grid, hipStream_t st) {
     atb_k<MODE, H, MODE == ATB_TYPED, true><<<grid, kGroupThreads, atb_lds_bytes(H), st>>>(a);
     return;
   }
-  const bool x6 = MODE == ATB_TYPED || MODE == ATB_PLAIN || (MODE == ATB_ROWS && a.rows_x6);   // PLAIN: no gate / column sums in the kernel -- it fits the file
-  if (g_exact_fp32 || !x6) atb_k<MODE, H, false><<<grid, kGroupThreads, atb_lds_bytes(H), st>>>(a);
-  else atb_k<MODE, H, true><<<grid, kGroupThreads, atb_lds_bytes(H), st>>>(a);
+  if constexpr (MODE == ATB_TYPED || MODE == ATB_PLAIN) {   // PLAIN: no gate / column sums in the kernel -- it fits the file
+    if (!g_exact_fp32) {
+      atb_k<MODE, H, true><<<grid, kGroupThreads, atb_lds_bytes(H), st>>>(a);
+      return;
+    }
+  }
+  atb_k<MODE, H, false><<<grid, kGroupThreads, atb_lds_bytes(H), st>>>(a);
 }
 
 inline unsigned atb_blocks(int64_t tiles, int H = 128) {
@@ -591,7 +595,7 @@ int dmp_rel_atb(const float *X, int64_t ldx, int64_t rows_x, const float *D, int
 }
 
 int dmp_atb_rows_masked(const float *A, int64_t lda, const float *B, int64_t ldb, const float *gate, const uint32_t *rowmask,
-                        int x6, int64_t rows, int M, int N, int H, float *partial, float *partial_colsum, void *stream) {
+                        int64_t rows, int M, int N, int H, float *partial, float *partial_colsum, void *stream) {
   if (rowmask && !gate) return DMP_ERR_BAD_ARG;
   if (H != 128 && H != 64) return DMP_ERR_UNSUPPORTED;
   if (rows < 0 || M <= 0 || N <= 0) return DMP_ERR_BAD_ARG;
@@ -605,7 +609,7 @@ int dmp_atb_rows_masked(const float *A, int64_t lda, const float *B, int64_t ldb
   AtbArgs a{};
   a.Z = A; a.ldz = lda; a.D = B; a.ldd = ldb; a.E = rows; a.plain_tiles = (int)((rows + kSub - 1) / kSub);
   a.gate = gate; a.pT = partial; a.pstride = (int64_t)M * N; a.ldp = N; a.pCS = partial_colsum; a.nb = N / H; a.cs_ld = M;
-  a.rowmask = rowmask; a.rows_x6 = x6 ? 1 : 0;
+  a.rowmask = rowmask;
   const dim3 grid(rows_blocks(rows, M, N, H), (unsigned)((M / H) * (N / H)));
   if (H == 128) {
     if (!lds_ready<ATB_ROWS, 128>()) return DMP_ERR_HIP;

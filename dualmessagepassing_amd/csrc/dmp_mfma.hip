@@ -33,9 +33,6 @@
 //     epilogue's stores are issued, so the wait for prefetched rows never sits behind younger stores;
 //     the barrier orders LDS only (__syncthreads would drain vmcnt);
 //   * 128-bit buffer stores with an SGPR offset read their data registers late (see voffC below).
-// An experimental second driver (PP = 1, dmp_dev_set_mfma_variant) pairs two wave groups in one
-// 512-thread workgroup and forces them half an iteration apart with barriers ("ping-pong"); it wins
-// on the bare GEMM but not with the fused epilogues, and is not used by default.
 //
 //   dmp_edge_fwd_fused   H1[e] = relu(Z W'[:, :H] + coefE[e] Z W'[:, H:] + P[selA e, 0:H] - P[selB e, H:2H] + b)
 //                        = the G GEMM + dmp_edge_combine(relu) of the fused layer in one pass
@@ -91,29 +88,28 @@ struct MfmaArgs {
 // two workgroups per CU instead of three), a staged tile is three bf16 planes (split once, by the staging thread).  At
 // 18 GFLOP per E-row launch the f32-input MFMA is as tight a bound as the kernel's bytes (114 us of matrix pipe at its
 // peak); on bf16x6 (43 us) the row masks' saved bytes become time.
-template <int NC, int EPI, int PP, int H = 128, bool X6 = false>
-__global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 1 ? 3 : 2))) void mfma_pp(MfmaArgs p) {
-  static_assert(H == 128 || (H == 64 && !PP), "H = 64: independent workgroups only");
-  static_assert(!X6 || (!PP && NC == 1 && (EPI == EPI_GATE_RES || EPI == EPI_RELU_BWD_G)), "bf16x6: the pipelined one-panel form");
-  constexpr int NG = PP ? 2 : 1;                            // wave groups per workgroup
-  constexpr int kGThreads = 2 * H;                          // threads of a wave group: H / 32 waves, one 32-column slice each
+template <int NC, int EPI, int H = 128, bool X6 = false>
+__global__ __launch_bounds__(2 * H, X6 ? 2 : (NC == 1 ? 3 : 2)) void mfma_pp(MfmaArgs p) {
+  static_assert(H == 128 || H == 64, "H = 128 or 64");
+  static_assert(!X6 || (NC == 1 && (EPI == EPI_GATE_RES || EPI == EPI_RELU_BWD_G)), "bf16x6: the pipelined one-panel form");
+  constexpr int kGThreads = 2 * H;                          // threads of a workgroup: H / 32 waves, one 32-column slice each
   constexpr int kStride = H + 4, kQ = H / 4, kHalf = H / 2, kSteps4 = H / 8;   // LDS row stride, float4 per row, k per lane half
   constexpr uint32_t kRowBytes = H * 4u;
   // kPipe (one panel, streamed epilogue operand: out_fwd / bwd_h1): one barrier per tile, the staging of the next
   // tile (second As buffer), the row requests of the tile after it and the epilogue operand requests of the NEXT
   // tile (second operand register set: streamed rows need a whole tile of latency) in the MFMA shadow.
-  constexpr bool kPipe = !PP && NC == 1 && (EPI == EPI_GATE_RES || EPI == EPI_RELU_BWD_G);
+  constexpr bool kPipe = NC == 1 && (EPI == EPI_GATE_RES || EPI == EPI_RELU_BWD_G);
   constexpr int NBUF = kPipe ? 2 : 1, NPAR = kPipe ? 3 : 2;
   // X6: a staged tile = three bf16 planes (hi | mid | lo), rows of kStrideD dwords (H bf16 + 8 of padding: conflict-free
   // ds_read_b128 of 8 consecutive k per lane, as in dmp_typed.hip)
   constexpr int kStrideD = (H + 8) / 2, kPlane = kSub * kStrideD, kGroups = kHalf / 8;
-  __shared__ __attribute__((aligned(16))) float As[NG * NBUF][X6 ? 3 * kPlane : kSub * kStride];
-  __shared__ float Cs[(H / 32) * NG][32 * kScrStride];
-  __shared__ uint32_t rowA[NG][NPAR][kSub], rowB[NG][NPAR][kSub];   // [group][tile parity (kPipe: tile % 3)][row]
-  __shared__ float rowS[NG][NPAR][kSub];
+  __shared__ __attribute__((aligned(16))) float As[NBUF][X6 ? 3 * kPlane : kSub * kStride];
+  __shared__ float Cs[H / 32][32 * kScrStride];
+  __shared__ uint32_t rowA[NPAR][kSub], rowB[NPAR][kSub];   // [tile parity (kPipe: tile % 3)][row]
+  __shared__ float rowS[NPAR][kSub];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
-  const int grp = PP ? wave >> 2 : 0, cs = PP ? wave & 3 : wave, gtid = threadIdx.x & (kGThreads - 1);
+  const int cs = wave, gtid = threadIdx.x & (kGThreads - 1);
   const int col = 32 * cs + li;
   float b[NC][X6 ? 1 : kHalf];
   Split8 B6[X6 ? kGroups : 1];                              // X6: fragment g = the pieces of k-steps kHalf h + 8 g .. + 7
@@ -148,7 +144,7 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
       for (int s = 0; s < kHalf; ++s) asm volatile("" ::"v"(b[q][X6 ? 0 : s]));  // loads complete here, not inside the loop
   }
   float4 colsum = make_float4(0.f, 0.f, 0.f, 0.f);  // EPI_RELU_BWD_G: this lane's 4 columns
-  float *As_g = As[grp * NBUF];
+  float *As_g = As[0];
   float *scr = Cs[wave];
 
   // per-lane constants of the wide (float4) layout: lane -> row 8k + lane/8, 4 columns from c4
@@ -183,9 +179,8 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
 
   // tile indices are 32-bit and wave-uniform (SGPRs)
   const int ntiles = (int)((p.E + kSub - 1) / kSub);
-  const int stride = (int)gridDim.x * NG;
-  const int first = (int)blockIdx.x * NG;
-  const int niter = first < ntiles ? (ntiles - first + stride - 1) / stride : 0;  // group 0's tile count (>= group 1's)
+  const int stride = (int)gridDim.x;
+  const int first = (int)blockIdx.x;
   auto tile_rows = [&](int t) {                            // valid rows of tile t (0 past the end), scalar
     const int64_t left = p.E - (int64_t)t * kSub;
     return (int)(left < 0 ? 0 : (left > kSub ? kSub : left));
@@ -238,8 +233,8 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
         bb = pre_b;
         a = pre_a * (uint32_t)(p.ldt * 4) + (bb ? kRowBytes : 0u);
       }
-      rowA[grp][par][gtid] = a; rowB[grp][par][gtid] = bb;
-      rowS[grp][par][gtid] = (EPI == EPI_GATE_RES && !p.rowscale) ? 1.f : pre_s;
+      rowA[par][gtid] = a; rowB[par][gtid] = bb;
+      rowS[par][gtid] = (EPI == EPI_GATE_RES && !p.rowscale) ? 1.f : pre_s;
     }
   };
 
@@ -259,7 +254,7 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
     }
   };
   auto stage_scalars_to = [&](int par) {
-    if (gtid < kSub) rowS[grp][par][gtid] = (EPI == EPI_GATE_RES && !p.rowscale) ? 1.f : pre_s;
+    if (gtid < kSub) rowS[par][gtid] = (EPI == EPI_GATE_RES && !p.rowscale) ? 1.f : pre_s;
   };
   auto load_scalars_of = [&](int t) {
     if (gtid < kSub) {
@@ -278,10 +273,10 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
     for (int k = 0; k < 4; ++k) {
       const int rr = 8 * k + lrow;
       if (EPI == EPI_EDGE) {
-        g0[k] = buf_load4(rs_T, rowA[grp][par][rr] + voffT, 0);
-        g1[k] = buf_load4(rs_T, rowB[grp][par][rr] + voffT, 0);
+        g0[k] = buf_load4(rs_T, rowA[par][rr] + voffT, 0);
+        g1[k] = buf_load4(rs_T, rowB[par][rr] + voffT, 0);
       } else if (EPI == EPI_DZ) {
-        g0[k] = buf_load4(rs_T, rowA[grp][par][rr] + voffT, 0);
+        g0[k] = buf_load4(rs_T, rowA[par][rr] + voffT, 0);
         g1[k] = buf_load4(rr_, voffR, k * grpR);
       } else if (EPI == EPI_RELU_BWD_G && kMasked) {
         g0[k] = buf_load4(rr_, voff_if(mask_of(t) >> (8 * k), rbit, voffR), k * grpR);
@@ -398,7 +393,7 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
       for (int r = 0; r < 16; ++r) {
         const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
         float v = acc[q][r];
-        if (EPI == EPI_EDGE || EPI == EPI_DZ) v = v + rowS[grp][par][rr] * acc[NC - 1][r];
+        if (EPI == EPI_EDGE || EPI == EPI_DZ) v = v + rowS[par][rr] * acc[NC - 1][r];
         scr[rr * kScrStride + li] = v;
       }
       if (EPI != EPI_NONE && !kEarly) fetch_operands(t, par);
@@ -414,25 +409,25 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
           v.z = act_fwd((v.z + (g0[k].z - g1[k].z)) + bias4.z, slope);
           v.w = act_fwd((v.w + (g0[k].w - g1[k].w)) + bias4.w, slope);
         } else if (EPI == EPI_DZ) {
-          const float sg = rowB[grp][par][rr] ? p.s1 : p.s0;
+          const float sg = rowB[par][rr] ? p.s1 : p.s0;
           v.x += g1[k].x + sg * g0[k].x; v.y += g1[k].y + sg * g0[k].y;
           v.z += g1[k].z + sg * g0[k].z; v.w += g1[k].w + sg * g0[k].w;
         } else if (EPI == EPI_GATE_RES) {
-          const float gt = rowS[grp][par][rr];
+          const float gt = rowS[par][rr];
           v.x = (v.x + bias4.x) * gt + g0[k].x; v.y = (v.y + bias4.y) * gt + g0[k].y;
           v.z = (v.z + bias4.z) * gt + g0[k].z; v.w = (v.w + bias4.w) * gt + g0[k].w;
         } else if (EPI == EPI_RELU_BWD_G) {
           // dPre = H1 > 0 ? dH1 : 0;  dG = [dPre | coef[dst] dPre];  column sums of dPre
           // (rows past the end: H1 reads as 0 -> dPre = 0, nothing stored)
           if (p.gated) {                                     // dO = gate * dOut: a row scale commutes with the product
-            const float gt = rowS[grp][par][rr];
+            const float gt = rowS[par][rr];
             v.x *= gt; v.y *= gt; v.z *= gt; v.w *= gt;
           }
           v.x = act_bwd(g0[k].x, v.x, slope); v.y = act_bwd(g0[k].y, v.y, slope);
           v.z = act_bwd(g0[k].z, v.z, slope); v.w = act_bwd(g0[k].w, v.w, slope);
           colsum.x += v.x; colsum.y += v.y; colsum.z += v.z; colsum.w += v.w;
           if (both_halves) {
-            const float cf = rowS[grp][par][rr];
+            const float cf = rowS[par][rr];
             buf_store4(make_float4(v.x * cf, v.y * cf, v.z * cf, v.w * cf), rc, (kMasked ? voff_if(mks >> (8 * k), rbit, voffC[k]) : voffC[k]) + kRowBytes, 0);
           }
         }
@@ -441,7 +436,7 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
     }
   };
 
-  const int t0 = first + grp;
+  const int t0 = first;
   const int mine = t0 < ntiles ? (ntiles - t0 + stride - 1) / stride : 0;
   auto tile = [&](int k) { return __builtin_amdgcn_readfirstlane(t0 + k * stride); };
   if (kPipe) {
@@ -466,7 +461,7 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
       for (int q = 0; q < 4; ++q) g0[q] = g0n[kPipe ? q : 0];
       par3 = par3 == 2 ? 0 : par3 + 1;
     }
-  } else if (!PP) {
+  } else {
     // Independent 256-thread workgroups (2-3 resident per CU, not synchronised with each other).
     // Per tile k:  MFMA phase | barrier | stage k+1, prefetch k+2 | barrier | epilogue k.
     // The wait for the prefetched rows in `stage` only has YOUNGER traffic behind it (the previous
@@ -485,45 +480,18 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
       lds_barrier();               // tile k+1 is in LDS for everyone
       epilogue(tile(k), par);
     }
-  } else {
-    // Both groups run the SAME step sequence, one step apart: in step s a group does its memory phase
-    // when (s + grp) is even (staging of its next tile, epilogue of the tile it computed last, prefetch
-    // of the tile after) and its MFMA phase when (s + grp) is odd.  Tile k of a group: first + grp + k*stride;
-    // tiles past the end are all-zero / dropped by the buffer range checks.
-    int staged = 0, computed = 0, stored = 0;
-    load_rows(tile(0));
-    for (int s = 0; s < 2 * niter + 2; ++s) {
-      if (((s + grp) & 1) == 0) {
-        // Staging first, the next prefetch last (one in-order vmcnt, see the header); unconditional,
-        // on one straight-line path, so that the compiler sees the prefetch registers as free and does
-        // not drain the epilogue's stores before reusing them.
-        stage(staged & 1);
-        ++staged;
-        if (stored < computed) {
-          epilogue(tile(stored), stored & 1);
-          ++stored;
-        }
-        load_rows(tile(staged));
-      } else if (computed < staged && computed < mine) {
-        if (EPI != EPI_NONE && kEarly) fetch_operands(tile(computed), computed & 1);
-        compute();
-        ++computed;
-      }
-      lds_barrier();
-    }
-
   }
 
   if (EPI == EPI_RELU_BWD_G) {
     // lanes with equal (lane & 7) hold the same 4 columns for 8 different rows: fixed-order
-    // xor-shuffle tree over lane>>3, then one partial row per (workgroup, group)
+    // xor-shuffle tree over lane>>3, then one partial row per workgroup
 #pragma unroll
     for (int off = 8; off < 64; off <<= 1) {
       colsum.x += __shfl_xor(colsum.x, off, 64); colsum.y += __shfl_xor(colsum.y, off, 64);
       colsum.z += __shfl_xor(colsum.z, off, 64); colsum.w += __shfl_xor(colsum.w, off, 64);
     }
     if (lane < 8)
-      *reinterpret_cast<float4 *>(p.partial + ((int64_t)blockIdx.x * NG + grp) * H + 32 * cs + lane * 4) = colsum;
+      *reinterpret_cast<float4 *>(p.partial + (int64_t)blockIdx.x * H + 32 * cs + lane * 4) = colsum;
     if (kPipe && p.partialA) {
       // the 8 threads that staged the same 4 columns (gtid % kQ), added in a fixed order through the tile buffer
       lds_barrier();
@@ -543,36 +511,28 @@ __global__ __launch_bounds__(PP ? kPPThreads : 2 * H, PP ? 1 : (X6 ? 2 : (NC == 
   }
 }
 
-inline unsigned pp_blocks(int64_t E) {
-  const int64_t pairs = ((E + kSub - 1) / kSub + 1) / 2;
-  return (unsigned)(pairs < 256 ? (pairs > 0 ? pairs : 1) : 256);
-}
-
-int g_variant = 0;  // development switch: 0 = independent workgroups, 1 = ping-pong pairs
-
 inline unsigned wg_blocks(int64_t E, int per_cu) {
   const int64_t ntiles = (E + kSub - 1) / kSub, cap = 256 * per_cu;
   return (unsigned)(ntiles < cap ? (ntiles > 0 ? ntiles : 1) : cap);
 }
 
 // the pipelined one-panel kernels (out_fwd, bwd_h1) at H = 128: on the bf16 pipe (two workgroups per CU) unless the
-// development switch asks for the exact f32 MFMA (dmp_dev_set_exact_fp32) or for the ping-pong variant
+// development switch asks for the exact f32 MFMA (dmp_dev_set_exact_fp32)
 template <int EPI> constexpr bool x6_kind() { return EPI == EPI_GATE_RES || EPI == EPI_RELU_BWD_G; }
-template <int NC, int EPI> inline bool x6_on() { return NC == 1 && x6_kind<EPI>() && g_variant == 0 && !g_exact_fp32; }
+template <int NC, int EPI> inline bool x6_on() { return NC == 1 && x6_kind<EPI>() && !g_exact_fp32; }
 template <int NC, int EPI>
 inline int launch_mfma(const MfmaArgs &p, hipStream_t st) {
-  if (g_variant == 1) mfma_pp<NC, EPI, 1><<<pp_blocks(p.E), kPPThreads, 0, st>>>(p);
-  else if constexpr (NC == 1 && x6_kind<EPI>()) {
-    if (x6_on<NC, EPI>()) mfma_pp<NC, EPI, 0, 128, true><<<wg_blocks(p.E, 2), kGroupThreads, 0, st>>>(p);
-    else mfma_pp<NC, EPI, 0><<<wg_blocks(p.E, 3), kGroupThreads, 0, st>>>(p);
-  } else mfma_pp<NC, EPI, 0><<<wg_blocks(p.E, NC == 1 ? 3 : 2), kGroupThreads, 0, st>>>(p);
+  if constexpr (NC == 1 && x6_kind<EPI>()) {
+    if (x6_on<NC, EPI>()) mfma_pp<NC, EPI, 128, true><<<wg_blocks(p.E, 2), kGroupThreads, 0, st>>>(p);
+    else mfma_pp<NC, EPI><<<wg_blocks(p.E, 3), kGroupThreads, 0, st>>>(p);
+  } else mfma_pp<NC, EPI><<<wg_blocks(p.E, NC == 1 ? 3 : 2), kGroupThreads, 0, st>>>(p);
   return check_launch();
 }
 // H = 64, one panel: 128-thread workgroups, 5 per CU (27 KB of LDS each)
 constexpr int kPerCU64 = 5;
 template <int EPI>
 inline int launch_mfma64(const MfmaArgs &p, hipStream_t st) {
-  mfma_pp<1, EPI, 0, 64><<<wg_blocks(p.E, kPerCU64), 128, 0, st>>>(p);
+  mfma_pp<1, EPI, 64><<<wg_blocks(p.E, kPerCU64), 128, 0, st>>>(p);
   return check_launch();
 }
 
@@ -754,24 +714,22 @@ int dmp_out_fwd_fused_rows(const float *Hin, int64_t ldh, const float *W2, int64
   p.A = Hin; p.lda = ldh; p.B = W2; p.ldb = ldw;
   p.bt = w_in_out ? 0 : 1;  // nn.Linear weight [out, in]: B[k][j] = W2[j][k]; [in, out] (its transpose): B[k][j] = W2[k][j]
   p.C = out; p.ldc = ldo; p.E = E; p.bias = bias; p.rowscale = gate; p.R = R; p.ldr = R ? ldr : H; p.ldt = 2 * H;
-  p.rowmask = g_variant == 1 ? nullptr : rowmask;
+  p.rowmask = rowmask;
   p.dead_rows = dead_rows;
   return H == 128 ? launch_mfma<1, EPI_GATE_RES>(p, (hipStream_t)stream) : launch_mfma64<EPI_GATE_RES>(p, (hipStream_t)stream);
 }
 
 static int64_t dmp_mfma_partial_rows(int64_t E) {      // = the grid of the EPI_RELU_BWD_G launch (bwd_h1): one partial row per workgroup
-  return g_variant == 1 ? 2 * (int64_t)pp_blocks(E) : (int64_t)wg_blocks(E, x6_on<1, EPI_RELU_BWD_G>() ? 2 : 3);
+  return (int64_t)wg_blocks(E, x6_on<1, EPI_RELU_BWD_G>() ? 2 : 3);
 }
 int64_t dmp_mfma_partial_rows_h(int64_t E, int H) { return H == 64 ? (int64_t)wg_blocks(E, kPerCU64) : dmp_mfma_partial_rows(E); }
-
-void dmp_dev_set_mfma_variant(int v) { g_variant = v; }
 
 int dmp_bwd_h1_fused_rows(const float *dO, int64_t ldo, const float *W2, int64_t ldw, const float *H1, int64_t ldh,
                           const float *coefE, const float *gate, const uint32_t *rowmask, int skip_dead_stores, int64_t E, int H,
                           float slope, float *dG, int64_t ldg, float *partial, float *partial_rows, void *stream) {
   if (rowmask && !gate) return DMP_ERR_BAD_ARG;
   if (skip_dead_stores && !rowmask) return DMP_ERR_BAD_ARG;
-  if (partial_rows && (g_variant == 1 || !aligned16(partial_rows))) return DMP_ERR_UNSUPPORTED;
+  if (partial_rows && !aligned16(partial_rows)) return DMP_ERR_UNSUPPORTED;
   if (H != 128 && H != 64) return DMP_ERR_UNSUPPORTED;
   if (E < 0) return DMP_ERR_BAD_ARG;
   if (!slope_ok(slope)) return DMP_ERR_UNSUPPORTED;
@@ -788,7 +746,7 @@ int dmp_bwd_h1_fused_rows(const float *dO, int64_t ldo, const float *W2, int64_t
   p.A = dO; p.lda = ldo; p.B = W2; p.ldb = ldw; p.bt = 0;  // dH1 = dO @ W2, W2 [out, in] = B[k = out][j = in]
   p.C = dG; p.ldc = ldg; p.E = E; p.R = H1; p.ldr = ldh; p.rowscale = gate ? gate : coefE; p.gated = gate != nullptr;
   p.both = both; p.partial = partial; p.ldt = 2 * H; p.slope = slope; p.partialA = partial_rows;
-  p.rowmask = g_variant == 1 ? nullptr : rowmask;
+  p.rowmask = rowmask;
   p.dead_rows = skip_dead_stores ? 2 : 0;
   return H == 128 ? launch_mfma<1, EPI_RELU_BWD_G>(p, (hipStream_t)stream) : launch_mfma64<EPI_RELU_BWD_G>(p, (hipStream_t)stream);
 }

@@ -11,7 +11,6 @@ constexpr int kLdsStride = 132;
 constexpr int kScrStride = 36;
 constexpr int kSub = 32;                                  // rows per tile / phase
 constexpr int kGroupThreads = 256;                        // 4 waves: one column slice each
-constexpr int kPPThreads = 2 * kGroupThreads;
 constexpr int kSubLoads = kSub * 32 / kGroupThreads;      // float4 loads per thread per tile (4)
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() is a fence over every address

@@ -10,7 +10,7 @@
 // H = 64 (the reference's shipped hidden_dim, config.py:298-301): the same kernel with H / 32 = 2 waves per
 // workgroup (one 32-column slice each), 32 k-steps per tile, twice the workgroups per CU.
 //
-// Structure as mfma_pp<1, EPI, 0> (dmp_mfma.hip): persistent 256-thread workgroups, 3 per CU, weight
+// Structure as mfma_pp<1, EPI> (dmp_mfma.hip): persistent 256-thread workgroups, 3 per CU, weight
 // panel W_g in registers (rebuilt only when the workgroup's contiguous tile range crosses into the
 // next class), buffer addressing with per-lane offsets, LDS-only barriers, three-deep prefetch
 // (ids of tile k+3, rows of tile k+2, staging of tile k+1 while tile k is computed).
@@ -578,8 +578,6 @@ __global__ __launch_bounds__(TypedGeom<H>::kThreads, 2) void mfma_typed_jobs(Typ
 }
 
 inline unsigned typed_blocks(int64_t tiles_bound, int per_cu = 3) {
-  static const int dev_per_cu = [] { const char *e = getenv("DMP_DEV_TYPED_PER_CU"); return e ? atoi(e) : 0; }();   // development probe
-  if (dev_per_cu > 0) per_cu = dev_per_cu;
   const int64_t cap = 256 * per_cu;
   return (unsigned)(tiles_bound < cap ? (tiles_bound > 0 ? tiles_bound : 1) : cap);
 }

@@ -361,10 +361,6 @@ def _joint_gates(v_gate, e_gate, np_, ep_, dtype, device):
     return vg, eg
 
 
-import os as _os
-PREFETCH_UNGATED = _os.environ.get("DMP_DEV_PREFETCH_UNGATED", "1") == "1"   # the side-stream index branch also without gates
-
-
 def prefetch_joint_indexes(model, pattern, graph, v_gate, e_gate, pool_kinds=(), skip_rev=True):
     """Everything ``joint_rep`` and its layers derive from the batch's STRUCTURE and its two filter gates alone, issued on the
     side stream (``side.fork``) as soon as the gates exist: the union graph and its CSR index, the degree coefficients, the
@@ -391,8 +387,6 @@ def prefetch_joint_indexes(model, pattern, graph, v_gate, e_gate, pool_kinds=(),
     if e_gate is None:
         # no filter net (the all-rows step): what is left is the structure itself -- the union's CSR, the coefficients and
         # selectors, the degree-class tiles of the typed kernels, the pooling indexes
-        if not PREFETCH_UNGATED:
-            return
         with side.fork() as forked:
             if not forked:
                 return
@@ -433,8 +427,7 @@ def prefetch_joint_indexes(model, pattern, graph, v_gate, e_gate, pool_kinds=(),
         want_nodes = bool(N >= 4096 and fused.onepanel_ok(H) and fused.USE_NODE_ROWS and fused.USE_PLAIN_ATB and fused.zero_rows_gate(vg) and typed and E > 0)
         want_l0 = bool(typed and fused.SKIP_DEAD_ROWS and fused.USE_ROW_MASKS and fused.USE_L0_ROW_LISTS and len(layers) > 1 and ep_ % 32 == 0
                        and E - ep_ >= fused.L0_LIST_MIN_ROWS and th.is_grad_enabled())
-        want_asc = bool(typed and fused.zero_rows_gate(eg) and fused.USE_PLAIN_ATB and getattr(eg, "_dmp_binary", False)
-                        and (fused.PLAIN_ROWS_ASCENDING or (fused.PLAIN_ATB_ASCENDING and th.is_grad_enabled())))
+        want_asc = bool(typed and fused.zero_rows_gate(eg) and fused.USE_PLAIN_ATB and getattr(eg, "_dmp_binary", False))
         fused.gate_bundle(ix, vg, eg, want_nodes, (ep_, E) if want_l0 else None, want_asc)
         nd = None
         if N >= 4096 and fused.onepanel_ok(H):
@@ -448,8 +441,7 @@ def prefetch_joint_indexes(model, pattern, graph, v_gate, e_gate, pool_kinds=(),
         side.mark("erows")
         if typed and fused.zero_rows_gate(eg):
             fused.live_tiles(ix, coef, eg)
-            if fused.PLAIN_ROWS_ASCENDING or (fused.PLAIN_ATB_ASCENDING and th.is_grad_enabled()):
-                fused.ascending_tiles(eg)                  # the plain-panel launches' row order
+            fused.ascending_tiles(eg)                  # the plain-panel launches' row order
             side.mark("tiles")
             fused.keep_in_csr(ix, eg)
             side.mark("keepcsr")
@@ -461,7 +453,7 @@ def prefetch_joint_indexes(model, pattern, graph, v_gate, e_gate, pool_kinds=(),
                 if getattr(built["edge"], "rows_in_order", False):
                     fused.pool_weight_sums(built["edge"], eg)     # ... and the gate's per-graph sums (the pooled second Linear's bias term)
         side.mark("pools")
-        if (nd is not None and typed and fused.USE_MASKED_SUMS and fused.USE_KEPT_INCIDENCE and fused.zero_rows_gate(eg) and H % 4 == 0
+        if (nd is not None and typed and fused.USE_MASKED_SUMS and fused.zero_rows_gate(eg) and H % 4 == 0
                 and fused.gate_row_mask(eg) is not None and th.is_grad_enabled()):
             nd.kept_incidence(ix, eg)
         side.mark("incidence")
@@ -593,7 +585,7 @@ def _layer0_codes(union, layers, p_v_emb, p_e_emb, g_v_emb, g_e_emb, v_gate, e_g
         return None
     shared = ps[1] is gs[1]
     pv, gv = getattr(p_v_emb, "_dmp_src", None), getattr(g_v_emb, "_dmp_src", None)
-    nodes = bool(fused.USE_LAYER0_NODES and pv is not None and gv is not None and gv[1].requires_grad and pv[1].requires_grad
+    nodes = bool(pv is not None and gv is not None and gv[1].requires_grad and pv[1].requires_grad
                  and (pv[1] is gv[1]) == shared and pv[0].size(0) == p_nodes and fused.l0_nodes_ok(H, pv[0], gv[0], pv[1], gv[1])
                  and (v_gate is None or (not v_gate.requires_grad and v_gate.numel() == gv[0].size(0))))
     specs = [(ps[0], gs[0], e_gate, False)]

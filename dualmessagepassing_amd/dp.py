@@ -261,9 +261,6 @@ def _warn_batch_norm(module, sync):
                       "the global batch" % (sync.world, ", ".join(bn[:3]), ", ..." if len(bn) > 3 else ""), RuntimeWarning, stacklevel=3)
 
 
-USE_SEGMENT_STEPS = True   # one AdamW step count per parameter tensor of a flat buffer
-
-
 class FlatAdamW(torch.optim.Optimizer):
     """``torch.optim.AdamW`` (optionally ``amsgrad``: the reference's optimizer, train.py:1231) whose step is
     ONE HIP launch per parameter tensor (``dmp_adamw_step``) -- meant for the single flat parameter of
@@ -389,7 +386,7 @@ class FlatAdamW(torch.optim.Optimizer):
                         st["max_exp_avg_sq"] = torch.zeros_like(p)
                 st["step"] += 1
                 seg = getattr(p, "_dmp_seg", None)
-                if seg is not None and USE_SEGMENT_STEPS and seg[1] <= 1024 and seg[0].device == p.device:
+                if seg is not None and seg[1] <= 1024 and seg[0].device == p.device:
                     # a flat buffer of parameter tensors: one step count per tensor (torch.optim.AdamW's state), on the device
                     import ctypes
                     dev, tab = self._segment_state(p, group, seg[1])

@@ -176,15 +176,12 @@ def pool_relu_bwd(table, rowmap, gate, act, pool, slope=0.0, skip_dead=False):
     return out, reduce_partials(part), Q
 
 
-USE_KEEP_POOL = True
-
-
 def keep_pool_csr(pool, gate):
     """``(ptr, ent)``: the chunk table of ``pool`` over the rows a 0 / 1 ``gate`` keeps (``dmp_csr_keep`` on the pooling index's
     chunk CSR), memoised on the gate per index, or None.  A pooled pass with a 0 / 1 row weight is then the PLAIN segment sum
     over 42 % of the entries (full load slots) instead of the weighted one that walks every entry: 46 -> 28 us at bench.py's
     shape; same sums, same order (the skipped rows added zeros)."""
-    if gate is None or not USE_KEEP_POOL or not USE_ROW_MASKS or pool.num_chunks == 0 or gate.numel() == 0:
+    if gate is None or not USE_ROW_MASKS or pool.num_chunks == 0 or gate.numel() == 0:
         return None
     owner = _gate_owner(gate)
     if getattr(owner, "_dmp_dense_gate", False) or not getattr(owner, "_dmp_binary", False):
@@ -315,19 +312,18 @@ def relu_bwd_g_colsum(d_h, act, coef, dst32, slope=0.0):
     return d_g, reduce_partials(part)
 
 
-USE_MFMA_KERNELS = True  # H == 128 / 64: fused MFMA kernels for the edge chain (csrc/dmp_mfma.hip)
 MFMA_WIDTHS = (128, 64)  # one-panel kernels (out_fwd, bwd_h1), class-typed kernels and the weight-gradient kernels
 
 
 def mfma_ok(index, H):
     """The fused MFMA kernels take H = 128 and address the gathered tables / per-edge arrays with
     32-bit byte offsets: [N, 3H] fp32 projections and E-float arrays must stay below 4 GiB."""
-    return USE_MFMA_KERNELS and H == 128 and index.num_nodes * 3 * H * 4 < 2 ** 32 and index.num_edges * 4 < 2 ** 32
+    return H == 128 and index.num_nodes * 3 * H * 4 < 2 ** 32 and index.num_edges * 4 < 2 ** 32
 
 
 def onepanel_ok(H):
     """out_fwd_mfma / bwd_h1_mfma (dPre alone) take this width (128, or the reference's shipped 64)."""
-    return USE_MFMA_KERNELS and H in MFMA_WIDTHS
+    return H in MFMA_WIDTHS
 
 
 def edge_fwd_mfma(z, Wes, P, ldp, bias, coef, index, slope=0.0):
@@ -344,14 +340,11 @@ def edge_fwd_mfma(z, Wes, P, ldp, bias, coef, index, slope=0.0):
     return out
 
 
-USE_TYPED_KERNELS = True  # degree-class tiles: one weight panel instead of two in edge_fwd / bwd_z (csrc/dmp_typed.hip)
-
-
 def typed_ok(index, H):
     """Class-typed kernels: rows are addressed by index (structured buffer descriptors), so the [E, H] arrays may be of
     any size (BASELINE config 4's 1024-pair shard: 8.4 M edge rows, 4.3 GB per array, one pass); what is 32-bit are the
     packed (row << 1 | flag) index entries and the per-edge int32 arrays."""
-    return USE_TYPED_KERNELS and onepanel_ok(H) and index.num_nodes < 2 ** 31 and index.num_edges < 2 ** 30
+    return onepanel_ok(H) and index.num_nodes < 2 ** 31 and index.num_edges < 2 ** 30
 
 
 def edge_fwd_typed(z, Wes, P, ldp, bias, coef, index, slope=0.0, dead_gate=None, sel=None):
@@ -433,13 +426,10 @@ def live_tiles(index, coef, gate):
     return res
 
 
-USE_KEEP_CSR = True
-
-
 def keep_in_csr(index, gate):
     """``(keep_ptr, keep_ent)``: ``index``'s CSR by destination over the edges a 0 / 1 ``gate`` keeps (``dmp_csr_keep``), memoised
     on the gate (the layers of a rep-net share it), or None."""
-    if gate is None or not USE_KEEP_CSR or not USE_ROW_MASKS or index.num_edges == 0:
+    if gate is None or not USE_ROW_MASKS or index.num_edges == 0:
         return None
     owner = _gate_owner(gate)
     if getattr(owner, "_dmp_dense_gate", False) or not getattr(owner, "_dmp_binary", False):
@@ -460,13 +450,6 @@ def keep_in_csr(index, gate):
     except Exception:
         pass
     return res
-
-
-# the launches over the kept edges' tiles whose panel does not depend on the degree class (second Linear forward / backward, its
-# weight gradient) walk the kept rows in ASCENDING order instead of class by class: the 512-byte row gathers then move through
-# memory front to back (measured on one box: atb_typed plain 81 -> 71 us, bwd_h1_typed 77 -> 72 us; -0.03 ms per step)
-PLAIN_ATB_ASCENDING = True
-PLAIN_ROWS_ASCENDING = True
 
 
 _ZEROS = {}
@@ -508,8 +491,10 @@ def identity_tiles(R, device):
 
 def ascending_tiles(gate):
     """The rows a 0 / 1 ``gate`` keeps as a tile slot list in ASCENDING row order (``dmp_kept_rows(tiles = 1)``; the class tiles list
-    them class by class): for products that need no class -- the plain weight gradient ``dO^T H1`` -- the row gathers then walk
-    memory front to back.  ``(slot, tile_scale (zeros), num_tiles, bound)`` or None; memoised on the gate."""
+    them class by class): for the launches over the kept edges' tiles whose panel does not depend on the degree class (the second
+    Linear forward / backward, its weight gradient ``dO^T H1``) the 512-byte row gathers then walk memory front to back (measured
+    on one box: atb_typed plain 81 -> 71 us, bwd_h1_typed 77 -> 72 us; -0.03 ms per step).  ``(slot, tile_scale (zeros), num_tiles,
+    bound)`` or None; memoised on the gate."""
     mask = binary_gate_mask(gate)
     if mask is None:
         return None
@@ -566,9 +551,6 @@ def bwd_z_typed(d_pre, ld_pre, Wes, d_s, base, coef, index, WesT=None, base_map=
     return out
 
 
-USE_DZW = _os.environ.get("DMP_DEV_DZW", "1") == "1"     # the edge chain's input gradient and its class-typed weight gradient in ONE launch (``dmp_bwd_z_w``)
-
-
 def bwd_z_w(d_pre, z, Wes, d_s, base, coef, index, WesT=None, base_map=None, gate=None, dead_rows=None, dst=None):
     """``(dz, dWes)`` = ``(bwd_z_typed(...), atb_typed(z, d_pre, ...))`` from one pass over ``d_pre`` (``dmp_bwd_z_w``: the two-role kernel
     of csrc/dmp_h1w.hip with the class-typed panel and the class emission), or None where it does not apply: it needs the kept edges'
@@ -576,7 +558,7 @@ def bwd_z_w(d_pre, z, Wes, d_s, base, coef, index, WesT=None, base_map=None, gat
     lib = _lib.load()
     E, H = d_pre.size(0), Wes.size(0)
     lim = (1 << 32) - 65536
-    if (not USE_DZW or (dead_rows is None) != (gate is None) or H != 128 or lib.dmp_dev_get_exact_fp32() or z is None or z.size(0) != E or E * H * 4 >= lim
+    if ((dead_rows is None) != (gate is None) or H != 128 or lib.dmp_dev_get_exact_fp32() or z is None or z.size(0) != E or E * H * 4 >= lim
             or E * d_pre.stride(0) * 4 >= lim or E * z.stride(0) * 4 >= lim or d_pre.data_ptr() % 16 or z.data_ptr() % 16
             or d_pre.stride(0) % 4 or z.stride(0) % 4 or index.num_nodes * d_s.size(1) * 4 >= lim):
         return None
@@ -606,7 +588,7 @@ def bwd_z_w(d_pre, z, Wes, d_s, base, coef, index, WesT=None, base_map=None, gat
     return out, reduce_partials(part).view(H, 2 * H)
 
 
-USE_ATB2 = _os.environ.get("DMP_DEV_ATB2", "1") == "1"     # the tile-list weight gradients on the bf16-piece LDS image (``dmp_atb2_jobs``)
+USE_ATB2 = True     # the tile-list weight gradients on the bf16-piece LDS image (``dmp_atb2_jobs``)
 
 
 class _Atb2Job(_ctypes.Structure):
@@ -653,7 +635,7 @@ def atb_typed(z, d_pre, coef, index, gate=None, plain=False):
     lib = _lib.load()
     E, H = z.shape
     lt = live_tiles(index, coef, gate)
-    if plain and lt is not None and PLAIN_ATB_ASCENDING:
+    if plain and lt is not None:
         at = ascending_tiles(gate)
         if at is not None:
             lt = at
@@ -759,10 +741,6 @@ def out_fwd_mfma(h1, W2, b2, gate, prev, W2t=None, dead_rows=0):
     return out
 
 
-USE_TYPED_ATB_ROWS = True
-USE_TYPED_ROWS = True   # out_fwd / bwd_h1 over the kept edges' tiles where dead rows need no store
-
-
 _TYPED_JOB = None
 
 
@@ -811,8 +789,7 @@ def l0_rows(l0, W0, z):
     return out
 
 
-USE_OUT_CODES_DENSE = _os.environ.get("DMP_DEV_OUT_CODES_DENSE", "1") == "1"   # ... also without a gate (over the identity tile list)
-USE_OUT_CODES = _os.environ.get("DMP_DEV_OUT_CODES", "1") == "1"   # the first layer's residual rows z0 = codes W_e as a K-extension of its second Linear
+USE_OUT_CODES = True   # the first layer's residual rows z0 = codes W_e as a K-extension of its second Linear
 
 
 def out_codes_ok(h1, enc, K, Wc):
@@ -888,14 +865,10 @@ def bwd_h1_typed(d_o, W2, h1, tiles, slope=0.0, out=None):
     return d_g, reduce_partials(part), reduce_partials(part_rows)
 
 
-USE_H1W_DENSE = True    # ... also where no gate applies (every row live): over the identity tile list
-USE_H1W = True    # the second edge Linear's backward as ONE launch (dPre and dO^T H1 from the same fetched rows, csrc/dmp_h1w.hip)
-
-
 def h1w_ok(d_o, h1, H):
     """The one-launch form of ``bwd_h1_typed`` + ``atb_typed(plain=True)`` applies: H = 128, the bf16x6 arithmetic, arrays below 4 GiB."""
     lib = _lib.load()
-    return (USE_H1W and H == 128 and not lib.dmp_dev_get_exact_fp32() and d_o.size(0) * d_o.stride(0) * 4 < (1 << 32) - 65536
+    return (H == 128 and not lib.dmp_dev_get_exact_fp32() and d_o.size(0) * d_o.stride(0) * 4 < (1 << 32) - 65536
             and h1.size(0) * h1.stride(0) * 4 < (1 << 32) - 65536 and d_o.size(0) * H * 4 < (1 << 32) - 65536)
 
 
@@ -1005,12 +978,11 @@ def atb_rows(a, b, gate=None, colsum=True):
         return reduce_partials(part).view(M, N), cs
     part_cs = torch.empty((G, M), dtype=torch.float32, device=a.device) if colsum else None
     with _lib.timed("atb_rows[M=%d,N=%d,R=%d]", (M, N, R), 4 * (M + N) * R + (4 * R if gate is not None else 0)):
-        check(lib.dmp_atb_rows_masked(ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(gate), ptr(gate_row_mask(gate)), ATB_ROWS_X6,
+        check(lib.dmp_atb_rows_masked(ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(gate), ptr(gate_row_mask(gate)),
                                       R, M, N, blk, ptr(part), ptr(part_cs), stream_ptr()), "dmp_atb_rows_masked")
     return reduce_partials(part).view(M, N), (reduce_partials(part_cs) if colsum else None)
 
 
-ATB_ROWS_X6 = 0   # the gated rows weight gradient on the bf16 pipe (csrc/dmp_atb.hip)
 SMALLK_MAX = 16
 
 
@@ -1076,7 +1048,6 @@ def smallk_atb_cols(x, d, d2=None, out=None, H=None, mask=None, rows=None):
 
 
 _SMALLK_JOB = None
-USE_SMALLK_JOBS = _os.environ.get("DMP_DEV_SMALLK_JOBS", "1") == "1"
 
 
 def smallk_atb_jobs(jobs, H):
@@ -1112,7 +1083,6 @@ L0_KMAX = 16
 # the joint rep-net pass hands the first layer the packed label codes instead of differentiable [E, H] rows
 # (dmpnn.joint_rep); DMP_LAYER0=0 keeps the general path
 USE_LAYER0 = _os.environ.get("DMP_LAYER0", "1") == "1"
-USE_LAYER0_NODES = True    # ... and the node rows' codes as well
 
 
 def l0_pack(enc_p, enc_g, gate=None, stacked=False):
@@ -1309,8 +1279,6 @@ def gate_bundle(index, v_gate, e_gate, want_nodes=False, l0_range=None, want_asc
 
 
 USE_NODE_ROWS = _os.environ.get("DMP_NODE_ROWS", "1") == "1"   # the node side of a layer over the nodes a 0 / 1 node gate keeps
-USE_KEPT_INCIDENCE = True     # ... and its backward's endpoint sums as a segment sum over the kept edges' incidence CSR
-USE_NODE_TILE_ATB = True      # ... and the node side's weight gradients over the kept nodes' tiles
 
 
 class NodeRows:
@@ -1382,9 +1350,6 @@ def node_rows(index, v_gate, H):
 # beside the rest of its backward +1 %, the first layer's pass over dPre / dZn beside the node side's short launches +0.7 %, the first
 # layer's input rows (a 119 MB store) on a second side lane beside the layer's first launches +0.6 %.  The side stream carries the small
 # index builds only.)
-USE_SMALLK_LIST = True      # the first layer's node-code weight gradient over the kept nodes' list (40 -> 30 us)
-S0_KEPT_ROWS = True         # the first layer's code sums over the kept nodes' rows only (15 -> 10 us)
-USE_L0_NODE_FWD = True     # the first layer's node side from the label codes as one pass (csrc/dmp_layer0.hip::l0_node_fwd_k)
 L0_NODE_MAX_COLS = 40      # code columns per node row that kernel holds in registers: VK + 2 K0
 
 
@@ -1745,7 +1710,6 @@ def fold_layers(layers):
 
 
 _GEMM_TYPES = None
-USE_SMALL_GEMM_JOBS = True
 SMALL_GEMM_MAX_ROWS = 1024     # output rows up to which a product goes into the small-product launch (latency-oriented: a column per thread)
 
 
@@ -1836,7 +1800,7 @@ class _FusedDMPLayer(torch.autograd.Function):
         if l0 is not None:     # sum of z over a node's edges = (sum of the label codes) W0
             enc0, K0 = l0.enc, l0.K
             tables = l0.tables(z.size(0), N)
-            if nd is not None and S0_KEPT_ROWS and enc0.size(1) % 4 == 0:
+            if nd is not None and enc0.size(1) % 4 == 0:
                 # (the code sums of the kept nodes only: every reader -- the node pass over the kept list, the backward's masked
                 # K-column products -- leaves the dead nodes' rows out)
                 S0 = ops.seg_sum_raw(enc0, index.in_ptr, index.in_ent, N, None, True, -1.0, 1.0,
@@ -1846,31 +1810,28 @@ class _FusedDMPLayer(torch.autograd.Function):
             # S = [S0_in W0 | S0_out W0] is never built:  S Bn = S0_in (W0 Bn_in) + S0_out (W0 Bn_out), two K-column products
             Kp = enc0.size(1)
             vcodes_f = l0.venc is not None
-            node_pass = (USE_L0_NODE_FWD and vcodes_f and USE_SMALL_GEMM_JOBS and H in MFMA_WIDTHS and l0.VK + 2 * K0 <= L0_NODE_MAX_COLS
-                         and W0.size(0) // K0 <= 2)
-            if USE_SMALL_GEMM_JOBS:   # the parameter-only products of this layer in ONE launch: W0 Bn_in, W0 Bn_out, W0 [A | B], WV0 Wx
-                TK = W0.size(0)
-                M0 = torch.empty((TK, 2 * H), dtype=torch.float32, device=z.device)
-                jobs = [(M0, [(W0, False, Wes, False)], None)]
-                if node_pass:
-                    # ... written straight into the node pass's packed matrix, one per embedding table: rows 0 .. VK-1 = WV0 Wx (three
-                    # column blocks), then K0 rows W0 Bn_in and K0 rows W0 Bn_out in the first block; zeros elsewhere
-                    VK = l0.VK
-                    WP = torch.zeros((TK // K0, L0_NODE_MAX_COLS, 3 * H), dtype=torch.float32, device=z.device)
-                    for t in range(TK // K0):
-                        WVt = WV0 if WV0.size(0) == VK else WV0[t * VK:(t + 1) * VK]
-                        jobs += [(WP[t, :VK], [(WVt, False, Wx, False)], None),
-                                 (WP[t, VK:VK + K0, :H], [(W0[t * K0:(t + 1) * K0], False, Bn[:H], False)], None),
-                                 (WP[t, VK + K0:VK + 2 * K0, :H], [(W0[t * K0:(t + 1) * K0], False, Bn[H:], False)], None)]
-                else:
-                    WB = torch.empty((2, TK, H), dtype=torch.float32, device=z.device)
-                    jobs += [(WB[0], [(W0, False, Bn[:H], False)], None), (WB[1], [(W0, False, Bn[H:], False)], None)]
-                    if vcodes_f:
-                        MV = torch.empty((WV0.size(0), 3 * H), dtype=torch.float32, device=z.device)
-                        jobs.append((MV, [(WV0, False, Wx, False)], None))
-                small_gemm_jobs(jobs)
+            node_pass = (vcodes_f and H in MFMA_WIDTHS and l0.VK + 2 * K0 <= L0_NODE_MAX_COLS and W0.size(0) // K0 <= 2)
+            # the parameter-only products of this layer in ONE launch: W0 Bn_in, W0 Bn_out, W0 [A | B], WV0 Wx
+            TK = W0.size(0)
+            M0 = torch.empty((TK, 2 * H), dtype=torch.float32, device=z.device)
+            jobs = [(M0, [(W0, False, Wes, False)], None)]
+            if node_pass:
+                # ... written straight into the node pass's packed matrix, one per embedding table: rows 0 .. VK-1 = WV0 Wx (three
+                # column blocks), then K0 rows W0 Bn_in and K0 rows W0 Bn_out in the first block; zeros elsewhere
+                VK = l0.VK
+                WP = torch.zeros((TK // K0, L0_NODE_MAX_COLS, 3 * H), dtype=torch.float32, device=z.device)
+                for t in range(TK // K0):
+                    WVt = WV0 if WV0.size(0) == VK else WV0[t * VK:(t + 1) * VK]
+                    jobs += [(WP[t, :VK], [(WVt, False, Wx, False)], None),
+                             (WP[t, VK:VK + K0, :H], [(W0[t * K0:(t + 1) * K0], False, Bn[:H], False)], None),
+                             (WP[t, VK + K0:VK + 2 * K0, :H], [(W0[t * K0:(t + 1) * K0], False, Bn[H:], False)], None)]
             else:
-                WB = torch.matmul(W0, Bn.view(2, H, H))                                              # [2, T K, H]
+                WB = torch.empty((2, TK, H), dtype=torch.float32, device=z.device)
+                jobs += [(WB[0], [(W0, False, Bn[:H], False)], None), (WB[1], [(W0, False, Bn[H:], False)], None)]
+                if vcodes_f:
+                    MV = torch.empty((WV0.size(0), 3 * H), dtype=torch.float32, device=z.device)
+                    jobs.append((MV, [(WV0, False, Wx, False)], None))
+            small_gemm_jobs(jobs)
             if node_pass:
                 # the whole node side before the second Linear in ONE pass over the codes: H1n and the two projection blocks
                 # (the kept nodes' H1n rows only; a dead node's projection rows are zeros)
@@ -1888,8 +1849,6 @@ class _FusedDMPLayer(torch.autograd.Function):
                     if n1 > n0:
                         torch.mm(S0[n0:n1, :K0], WB[0, t * K0:(t + 1) * K0], out=SB[n0:n1])
                         SB[n0:n1].addmm_(S0[n0:n1, Kp:Kp + K0], WB[1, t * K0:(t + 1) * K0])
-            if not USE_SMALL_GEMM_JOBS:
-                M0 = W0 @ Wes                                                                        # [T K, 2H] = W0 [A | B]
             S = None
         else:
             # (input rows under a zero of a gate whose maker wiped them -- ``_dmp_zero_rows`` -- are zeros: not fetched)
@@ -1921,8 +1880,6 @@ class _FusedDMPLayer(torch.autograd.Function):
             pass
         elif l0 is not None and l0.venc is not None:     # x Wx = venc (WV0 Wx): three column blocks of K-column products
             VK = l0.VK
-            if not USE_SMALL_GEMM_JOBS:
-                MV = WV0 @ Wx                                                                        # [T VK, 3H]
             XP = torch.empty((N, 3 * H), dtype=torch.float32, device=z.device)
             for t, (n0, n1) in l0.vtables(N):
                 smallk_embed(l0.venc[n0:n1, :VK], MV[t * VK:(t + 1) * VK], None, XP[n0:n1], H)
@@ -1979,17 +1936,17 @@ class _FusedDMPLayer(torch.autograd.Function):
             # is the only reader of zn) the output's zero rows are not stored either
             dead = (3 if (inner & 1) else 1) if (dead_gate is not None and zero_rows_gate(e_gate)) else 0
             side.wait("tiles")
-            lt = live_tiles(index, coef, e_gate) if (dead == 3 and USE_TYPED_ROWS and eW2t is not None) else None
+            lt = live_tiles(index, coef, e_gate) if (dead == 3 and eW2t is not None) else None
             if lt is not None:      # nothing to write for the rows under a zero gate: the kept edges' tiles only
                 # (a plain panel needs no class: the kept edges' tiles in ascending row order -- ``ascending_tiles``)
-                tl_ = (ascending_tiles(e_gate) if PLAIN_ROWS_ASCENDING else None) or lt
+                tl_ = ascending_tiles(e_gate) or lt
                 if l0 is not None and residual and getattr(l0, "z_from_codes", False) and out_codes_ok(H1e, l0.enc, l0.K, W0[-l0.K:]):
                     # the target's residual rows z = enc W0 are not in memory at all (``dmpnn.joint_rep`` did not make them): one more
                     # k-group over their codes; the pattern's few rows (their own table) come in as the residual operand
                     zn = out_fwd_typed_codes(H1e, eW2t, eb2, l0.enc, l0.K, W0[-l0.K:], tl_, prev=l0.z_head, row0=l0.z_head.size(0))
                 else:
                     zn = out_fwd_typed(H1e, eW2t, eb2, l0_rows(l0, W0, z) if residual else None, tl_)
-            elif (l0 is not None and residual and e_gate is None and getattr(l0, "z_from_codes", False) and eW2t is not None and USE_TYPED_ROWS
+            elif (l0 is not None and residual and e_gate is None and getattr(l0, "z_from_codes", False) and eW2t is not None
                   and out_codes_ok(H1e, l0.enc, l0.K, W0[-l0.K:]) and identity_tiles(H1e.size(0), H1e.device) is not None):
                 # no gate at all (the all-rows step): the same launch over the identity tile list
                 zn = out_fwd_typed_codes(H1e, eW2t, eb2, l0.enc, l0.K, W0[-l0.K:], identity_tiles(H1e.size(0), H1e.device), prev=l0.z_head,
@@ -2018,7 +1975,7 @@ class _FusedDMPLayer(torch.autograd.Function):
             # (z's rows under a zero of a gate whose maker wiped the input are zeros, and as an inner layer's output not even
             # written: weight 0, not fetched)
             zs = pool_rows(z, epool, e_gate if zero_rows_gate(e_gate) else None).view(G_ * halves, H) if residual else None
-            if USE_SMALL_GEMM_JOBS and Q.is_contiguous() and eW2.is_contiguous() and Q.size(0) <= SMALL_GEMM_MAX_ROWS:
+            if Q.is_contiguous() and eW2.is_contiguous() and Q.size(0) <= SMALL_GEMM_MAX_ROWS:
                 es = torch.empty((G_ * halves, H), dtype=torch.float32, device=Q.device)  # Q W2^T + cnt b2 (+ sum of z): one launch
                 small_gemm_jobs([(es, [(Q, False, eW2, True), (cnt, False, eb2.view(1, H), False)], zs)])
             else:
@@ -2081,8 +2038,7 @@ class _FusedDMPLayer(torch.autograd.Function):
                     # (dPre's rows under a zero of a 0 / 1 gate: every reader below leaves them out -- the kept incidence sums,
                     # the class-tile kernels over the kept edges' tiles)
                     skip = (typed and USE_MASKED_SUMS and SKIP_DEAD_ROWS and ctx.l0 is None and binary_gate_mask(ctx.e_gate) is not None
-                            and zero_rows_gate(ctx.e_gate) and live_tiles(ix, coef, ctx.e_gate) is not None and nd is not None
-                            and USE_KEPT_INCIDENCE)
+                            and zero_rows_gate(ctx.e_gate) and live_tiles(ix, coef, ctx.e_gate) is not None and nd is not None)
                     dG, dbe, Q = pool_relu_bwd(T @ eW2, emap, ctx.e_gate, H1e, ep, slope, skip_dead=skip)       # dG is dPre; one pass over H1e
                     Q = Q[:, :H]
                 else:
@@ -2103,26 +2059,21 @@ class _FusedDMPLayer(torch.autograd.Function):
                     # leave them out)
                     skip = (USE_MASKED_SUMS and SKIP_DEAD_ROWS and gate_row_mask(ctx.e_gate) is not None
                             and (ctx.l0 is None or getattr(ctx.l0, "enc_mask", None) is not None))
-                    lt = live_tiles(ix, coef, ctx.e_gate) if (skip and USE_TYPED_ROWS) else None
-                    dW2e = None
-                    if lt is not None and USE_TYPED_ATB_ROWS and h1w_ok(dzn, H1e, H):
+                    lt = live_tiles(ix, coef, ctx.e_gate) if skip else None
+                    if lt is not None and h1w_ok(dzn, H1e, H):
                         # both products of the second Linear's backward from ONE pass over dO and H1 (csrc/dmp_h1w.hip)
-                        dG, dbe, db2e, dW2e = bwd_h1_w(dzn, eW2, H1e, (ascending_tiles(ctx.e_gate) if PLAIN_ROWS_ASCENDING else None) or lt, slope)
+                        dG, dbe, db2e, dW2e = bwd_h1_w(dzn, eW2, H1e, ascending_tiles(ctx.e_gate) or lt, slope)
                     elif lt is not None:      # over the kept edges' tiles only
-                        dG, dbe, db2e = bwd_h1_typed(dzn, eW2, H1e, (ascending_tiles(ctx.e_gate) if PLAIN_ROWS_ASCENDING else None) or lt, slope)
-                    else:
-                        dG, dbe, db2e = bwd_h1_mfma(dzn, eW2, H1e, coef, ix, both_halves=False, gate=ctx.e_gate, slope=slope, rows_colsum=True,
-                                                    skip_dead_stores=skip)
-                    if dW2e is not None:
-                        pass
-                    elif lt is not None and USE_TYPED_ATB_ROWS:
+                        dG, dbe, db2e = bwd_h1_typed(dzn, eW2, H1e, ascending_tiles(ctx.e_gate) or lt, slope)
                         # dO^T H1 over the kept edges' tiles: the class-tile weight-gradient kernel's first half (its class-scaled
                         # second half costs no further products) -- no tiles' worth of zero rows in between
                         dW2e = atb_typed(dzn, H1e, coef, ix, gate=ctx.e_gate, plain=True)
                     else:
+                        dG, dbe, db2e = bwd_h1_mfma(dzn, eW2, H1e, coef, ix, both_halves=False, gate=ctx.e_gate, slope=slope, rows_colsum=True,
+                                                    skip_dead_stores=skip)
                         dW2e = atb_rows(dzn, H1e, ctx.e_gate, colsum=False)[0]
                 else:
-                    it = identity_tiles(dzn.size(0), dzn.device) if (ctx.e_gate is None and USE_H1W_DENSE and h1w_ok(dzn, H1e, H)) else None
+                    it = identity_tiles(dzn.size(0), dzn.device) if (ctx.e_gate is None and h1w_ok(dzn, H1e, H)) else None
                     if it is not None:
                         # no gate at all (a model without a filter net: the reference's one-label datasets): every row is live --
                         # both products of the second Linear's backward in one launch over the identity tile list
@@ -2144,7 +2095,7 @@ class _FusedDMPLayer(torch.autograd.Function):
             # dPre into both endpoints' rows: the backward scatter-add (dPre's rows under a zero edge gate are zeros: not fetched)
             sums_masked = typed and USE_MASKED_SUMS and ctx.e_gate is not None and gate_row_mask(ctx.e_gate) is not None
             # (... and the rows of the dead nodes are neither summed nor stored)
-            if nd is not None and sums_masked and USE_KEPT_INCIDENCE and zero_rows_gate(ctx.e_gate) and H % 4 == 0:
+            if nd is not None and sums_masked and zero_rows_gate(ctx.e_gate) and H % 4 == 0:
                 # every kept node's two sums over its KEPT edges (the incidence CSR over the kept edges, a row per kept node):
                 # the plain segment-sum kernel, ascending edge id -- an edge row without a kept endpoint is never fetched
                 kp, ke = nd.kept_incidence(ix, ctx.e_gate)
@@ -2173,7 +2124,7 @@ class _FusedDMPLayer(torch.autograd.Function):
                 # (dG = dPre has zero rows under a zero edge gate, whichever kernel made it: the typed kernels skip those edges)
                 # (with the input gradient still to come -- ``dz`` below, over the same tile list -- both products of dPre run in ONE
                 # launch there, ``bwd_z_w``: decided here, made there)
-                fuse_dzw = bool(typed and USE_DZW and ctx.needs_input_grad[4] and H == 128 and
+                fuse_dzw = bool(typed and ctx.needs_input_grad[4] and H == 128 and
                                 (ctx.e_gate is None or (SKIP_DEAD_ROWS and zero_rows_gate(ctx.e_gate) and live_tiles(ix, coef, ctx.e_gate) is not None)))
                 dWes = None if fuse_dzw else (atb_typed(z, dG, coef, ix, gate=ctx.e_gate) if typed else atb(z, dG))   # [H,2H] = [dA_e | dB_e]
             # ---- node side
@@ -2210,7 +2161,7 @@ class _FusedDMPLayer(torch.autograd.Function):
                 Xn = (torch.empty if full else torch.zeros)((2, TK, H), dtype=torch.float32, device=dPn.device)
                 xjobs = [(S0[n0:n1, h * Kp:h * Kp + K0], dPn[n0:n1], Xn[h, t * K0:(t + 1) * K0],
                           nd.mask[n0 // 32:] if nd is not None else None) for t, _, (n0, n1) in tables if n1 > n0 for h in (0, 1)]
-                if USE_SMALLK_JOBS and 0 < len(xjobs) <= 4 and dPn.stride(1) == 1 and dPn.stride(0) % 2 == 0 and dPn.data_ptr() % 8 == 0:
+                if 0 < len(xjobs) <= 4 and dPn.stride(1) == 1 and dPn.stride(0) % 2 == 0 and dPn.data_ptr() % 8 == 0:
                     smallk_atb_jobs(xjobs, H)          # both tables x both halves: one launch
                     xjobs = []
                 for t, _, (n0, n1) in (tables if xjobs else []):
@@ -2232,16 +2183,16 @@ class _FusedDMPLayer(torch.autograd.Function):
                     for t, (n0, n1) in l0.vtables(N):
                         # (the packed node codes carry the node gate: a gated-out node's code row is all zeros)
                         # (one table over all nodes under the node gate: the kept nodes' list -- a node outside it has a zero code row)
-                        klist = nd.rows if (nd is not None and n0 == 0 and n1 == N and USE_SMALLK_LIST) else None
+                        klist = nd.rows if (nd is not None and n0 == 0 and n1 == N) else None
                         smallk_atb_cols(l0.venc[n0:n1, :VK], dXP[n0:n1], dxn[n0:n1] if ctx.residual else None,
                                         Yn[:, t * VK:(t + 1) * VK], H,
                                         mask=vmask[n0 // 32:] if (klist is None and vmask is not None and n0 % 32 == 0) else None, rows=klist)
                 elif one_launch:
                     vm = binary_gate_mask(ctx.v_gate)
-                    if nd is not None and USE_NODE_TILE_ATB:     # over the kept nodes' tiles
+                    if nd is not None:     # over the kept nodes' tiles
                         (dW2n, _), (dWx, _) = atb_rows_multi([(dxn, H1n, None, False), (x, dXP, None, False)], tiles=nd.tiles)
                     elif vm is not None:    # (db2n came from bwd_h1; no job carries a gate: the launch runs on the bf16 pipe)
-                        (dW2n, _), (dWx, _) = atb_rows_multi([(dxn, H1n, None, False, vm), (x, dXP, None, False, vm if nd is not None else None)])
+                        (dW2n, _), (dWx, _) = atb_rows_multi([(dxn, H1n, None, False, vm), (x, dXP, None, False)])
                     else:
                         (dW2n, db2n), (dWx, _) = atb_rows_multi([(dxn, H1n, ctx.v_gate, True, gate_row_mask(ctx.v_gate)), (x, dXP, None, False)])
                 else:
@@ -2260,15 +2211,14 @@ class _FusedDMPLayer(torch.autograd.Function):
                 if one_launch:   # the three node-side weight gradients (1 + 2 + 3 output blocks) share one launch
                     # (dPn = act'(H1n) ((v_gate dxn) W2): zero rows under a zero node gate -- the first two products skip them)
                     vm = gate_row_mask(ctx.v_gate)
-                    if nd is not None and USE_NODE_TILE_ATB:
+                    if nd is not None:
                         # the three products over the kept nodes' tiles (rows gathered by slot): 41 % of the row tiles at
                         # bench.py's labels, and nothing of a dead node's (unwritten) rows is touched
                         (dW2n, _), (dBn, _), (dWx, _) = atb_rows_multi([(dxn, H1n, None, False), (S, dPn, None, False), (x, dXP, None, False)],
                                                                         tiles=nd.tiles)
                     elif binary_gate_mask(ctx.v_gate) is not None:   # (db2n came from bwd_h1; no job carries a gate: bf16 pipe)
-                        # (under ``nd`` x's and dXP's rows of the dead nodes were never written: the third product skips them too)
                         (dW2n, _), (dBn, _), (dWx, _) = atb_rows_multi([(dxn, H1n, None, False, vm), (S, dPn, None, False, vm),
-                                                                         (x, dXP, None, False, vm if nd is not None else None)])
+                                                                         (x, dXP, None, False)])
                     else:
                         (dW2n, db2n), (dBn, _), (dWx, _) = atb_rows_multi([(dxn, H1n, ctx.v_gate, True, vm), (S, dPn, None, False, vm),
                                                                             (x, dXP, None, False)])
@@ -2319,7 +2269,7 @@ class _FusedDMPLayer(torch.autograd.Function):
                                                base=dzn if ctx.residual else None)
                     dz.addmm_(dG, Wes.t())
         dW0 = dWV0 = None
-        if l0 is not None and USE_SMALL_GEMM_JOBS:       # after the reductions of the block above have run: ONE launch
+        if l0 is not None:       # after the reductions of the block above have run: ONE launch
             # dWes = W0^T (enc^T [dPre | c dPre]);  dBn_h = W0^T X_h;  enc^T dz = (enc^T [dPre | c dPre]) [A | B]^T + sum_h X_h Bn_h^T
             # (+ enc^T dzn);  dWx = WV0^T (venc^T dXP) block by block;  venc^T dx = sum_b Y_b Wx_b^T (+ venc^T dxn)
             dev = XX.device
@@ -2337,16 +2287,6 @@ class _FusedDMPLayer(torch.autograd.Function):
                     jobs.append((dWx[:, b3 * H:(b3 + 1) * H], [(WV0, True, Yn[b3], False)], None))
                 jobs.append((dWV0, [(Yn[b3], False, Wx[:, b3 * H:(b3 + 1) * H], True) for b3 in range(3)], Yn[3] if ctx.residual else None))
             small_gemm_jobs(jobs)
-        elif l0 is not None:
-            dWes = W0.t() @ XX[:, :2 * H]                                  # z^T [dPre | c dPre] = W0^T (enc^T [dPre | c dPre])
-            dBn = torch.matmul(W0.t(), Xn).view(2 * H, H)
-            T3 = torch.bmm(Xn, Bn.view(2, H, H).transpose(1, 2)).sum(0)
-            # enc^T dz = enc^T dzn + (enc^T [dPre | c dPre]) [A | B]^T + (sum of enc)^T dS
-            dW0 = torch.addmm(T3 + XX[:, 2 * H:] if ctx.residual else T3, XX[:, :2 * H], Wes.t())
-            if vcodes:
-                Y = Yn[:3].transpose(0, 1).reshape(WV0.size(0), 3 * H)     # venc^T dXP  [T VK, 3H]
-                dWx = WV0.t() @ Y
-                dWV0 = torch.addmm(Yn[3], Y, Wx.t()) if ctx.residual else Y @ Wx.t()
         return (None, None, None, dx, dz, None, None, dBn, dbn, dWx, dWes, dbe, dW2n, db2n, dW2e, db2e, None, None, None, None,
                 None, None, None, dW0, dWV0, None, None)
 
@@ -2356,7 +2296,7 @@ def l0_z_from_codes(index, H, eg, l0, live_edges, residual):
     a residual layer and the conditions under which its second Linear runs over the kept edges' tiles (``l0_dead_inputs``' edge
     half) -- or without any edge gate, over all rows -- that launch adds ``enc W`` as one more k-group (``out_fwd_typed_codes``).
     (A layer that ends up elsewhere makes the rows itself: ``l0_rows``.)"""
-    return bool(USE_OUT_CODES and (live_edges or (eg is None and USE_OUT_CODES_DENSE and USE_TYPED_ROWS)) and residual and l0 is not None and H == 128
+    return bool(USE_OUT_CODES and (live_edges or eg is None) and residual and l0 is not None and H == 128
                 and not _lib.load().dmp_dev_get_exact_fp32() and l0.enc.stride(0) % 4 == 0 and l0.enc.data_ptr() % 16 == 0
                 and index.num_edges * 128 * 4 < (1 << 32) - 65536)
 
@@ -2366,7 +2306,7 @@ def l0_dead_inputs(index, H, vg, eg, l0):
     union's 0 / 1 gates?  The layer reads its edge rows ``z`` only as the residual term of its second Linear -- over the kept
     edges' tiles when the conditions below hold (the ones ``_FusedDMPLayer.forward`` tests) -- and its node rows ``x`` (with
     node codes) only as the residual term over the kept nodes' tiles."""
-    if l0 is None or not SKIP_DEAD_ROWS or not USE_ROW_MASKS or not USE_TYPED_ROWS or not typed_ok(index, H):
+    if l0 is None or not SKIP_DEAD_ROWS or not USE_ROW_MASKS or not typed_ok(index, H):
         return False, False
     edges = bool(eg is not None and zero_rows_gate(eg) and gate_row_mask(eg) is not None and USE_LIVE_TILES
                  and getattr(index, "_coef_deg", None) is not None)

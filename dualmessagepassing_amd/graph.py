@@ -33,9 +33,6 @@ class function:  # namespace mirroring ``import dgl.function as fn``
     sum = SumReducer
 
 
-USE_GRAPH_CSR = True   # block-diagonal batches: both CSRs from ONE launch (dmp_csr_build_graphs)
-
-
 class GraphIndex:
     """Device-resident integer index of one (batched) graph.
 
@@ -453,7 +450,7 @@ class BatchedGraph:
         key = None if rev is None else (rev.data_ptr(), rev._version)
         if self._index is None or self._index_key != key:
             offsets = None
-            if (USE_GRAPH_CSR and self.is_batched_on_device() and getattr(self, "max_num_nodes", None) is not None
+            if (self.is_batched_on_device() and getattr(self, "max_num_nodes", None) is not None
                     and self.max_num_nodes <= _lib.load().dmp_csr_build_graphs_max_nodes()
                     and int(self.node_offsets.numel()) - 1 == int(self.edge_offsets.numel()) - 1 > 0):
                 offsets = (self.node_offsets, self.edge_offsets, int(self.node_offsets.numel()) - 1)

@@ -416,7 +416,6 @@ class SmallLikePairs(PairDataset):
 
 _CRIT = {"MAE": F.l1_loss, "MSE": F.mse_loss, "SMSE": F.smooth_l1_loss}
 _CRIT_KIND = {"MSE": 0, "MAE": 1, "SMSE": 2}
-USE_FUSED_COUNT_LOSS = True
 
 
 class _CountLossHIP(torch.autograd.Function):
@@ -445,7 +444,7 @@ def count_loss(pred, target, bp_loss="MSE", neg_slope=1.0):
     """The count loss of train.py:624-628, ``bp_crit(F.leaky_relu(pred, neg_slope), target)`` with reduction 'mean'
     (``neg_slope`` 1: the plain criterion).  On the GPU, for fp32 tensors of equal size, the criterion, its mean and the
     gradient seed are ONE launch (five as tensor ops); anything else goes through the tensor ops."""
-    if (USE_FUSED_COUNT_LOSS and bp_loss in _CRIT_KIND and pred.is_cuda and pred.dtype == torch.float32 and torch.is_tensor(target)
+    if (bp_loss in _CRIT_KIND and pred.is_cuda and pred.dtype == torch.float32 and torch.is_tensor(target)
             and target.is_cuda and target.dtype == torch.float32 and not target.requires_grad and target.numel() == pred.numel()
             and 0 < pred.numel() <= (1 << 22) and 0.0 <= float(neg_slope) <= 1.0
             and pred.reshape(-1).shape == target.reshape(-1).shape and (pred.dim() == target.dim() or pred.dim() == 1 or target.dim() == 1)):

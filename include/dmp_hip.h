@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 88
+#define DMP_ABI_VERSION 89
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1282,10 +1282,9 @@ int dmp_atb_typed(const float *Z, int64_t ldz, const float *dPre, int64_t ldp,
 /* The same with H x H output blocks, H = 128 (the two functions above) or 64: M and N multiples of H. */
 int64_t dmp_atb_rows_blocks_h(int64_t rows, int M, int N, int H);
 /* dmp_atb_rows_masked with a row mask (dmp_row_mask_bits of the gate: the rows under a zero gate, which contribute gate * a = 0 to
- * every sum, are not fetched) and the choice of the matrix pipe: x6 != 0 = bf16x6 (fp32-accurate, dmp_dev_set_exact_fp32
- * overrides), 0 = the f32-input MFMA. */
+ * every sum, are not fetched), on the f32-input MFMA (the gated form does not fit the register file on the bf16 pipe). */
 int dmp_atb_rows_masked(const float *A, int64_t lda, const float *B, int64_t ldb, const float *gate, const uint32_t *rowmask,
-                        int x6, int64_t rows, int M, int N, int H, float *partial, float *partial_colsum, void *stream);
+                        int64_t rows, int M, int N, int H, float *partial, float *partial_colsum, void *stream);
 /* The rows product without a gate and without column sums, over the rows of a row mask (NULL: all): A^T B restricted to the masked-in
  * rows -- which IS (gate (.) A)^T B for a 0 / 1 gate whose mask it is.  On the bf16 pipe (bf16x6; the gated form above does not fit the
  * register file there); the bias gradient (column sums of the gated A) comes from dmp_smallk_atb_cols_masked with the gate as its
@@ -1342,11 +1341,6 @@ int dmp_atb_rows_jobs_h(const dmp_atb_job *jobs, int num_jobs, int64_t rows, int
                         const float *tile_scale, const int32_t *num_tiles, int64_t tiles_bound, void *stream);
 /* (a launch none of whose jobs has a gate or column sums runs on the bf16 pipe, bf16x6: the 0 / 1-gated products of a step come as
  * row masks, their column sums from dmp_bwd_h1_fused_rows (partial_rows)) */
-
-/* Development switch (not part of the product path): 0 = independent 256-thread workgroups (default),
- * 1 = the experimental "ping-pong" driver of csrc/dmp_mfma.hip (two wave groups per 512-thread workgroup
- * held half an iteration apart by barriers).  Process-wide; results are identical. */
-void dmp_dev_set_mfma_variant(int variant);
 
 
 /* Arithmetic of the class-typed kernels' products (dmp_edge_fwd_typed, dmp_bwd_z_typed_arow, dmp_rel_gemm).  Default (0):
