@@ -246,15 +246,27 @@ class DMPNN(nn.Module):
         return cached[1]
 
 
+ENCODERS = ("DMPNN", "RGCN", "RGIN")
+
+
 class TrainModel(nn.Module):
     """UNC ``TrainModel`` (model.py:631-744): the DMPNN encoder with ``2 * num_rels`` edge types plus
-    the link-prediction (DistMult score) or node-classification head and their regularisers."""
+    the link-prediction (DistMult score) or node-classification head and their regularisers.  ``encoder``: "DMPNN", or the
+    baselines "RGCN" / "RGIN" of Model/R-GCN and Model/R-GIN (``unc_rel``; the same head, their own encoder)."""
 
     def __init__(self, node_attri, num_nodes, o_dim, num_rels, nlabel, num_hidden_layers=1, dropout=0,
-                 use_cuda=False, reg_param=0):
+                 use_cuda=False, reg_param=0, encoder="DMPNN"):
         super(TrainModel, self).__init__()
+        if encoder not in ENCODERS:
+            raise ValueError("TrainModel: encoder must be one of %s, not %r" % (", ".join(ENCODERS), encoder))
         i_dim = o_dim if node_attri is None else node_attri.shape[1]
-        self.model = DMPNN(node_attri, None, num_nodes, i_dim, o_dim, num_rels * 2, num_hidden_layers, dropout, use_cuda)
+        if encoder == "DMPNN":
+            self.model = DMPNN(node_attri, None, num_nodes, i_dim, o_dim, num_rels * 2, num_hidden_layers, dropout, use_cuda)
+        else:
+            from . import unc_rel
+            cls = unc_rel.RGCN if encoder == "RGCN" else unc_rel.RGIN
+            self.model = cls(node_attri, None, num_nodes, i_dim, o_dim, num_rels * 2, num_hidden_layers, dropout, use_cuda)
+        self.encoder = encoder
         self.reg_param = reg_param
         if nlabel == 0:
             self.supervised = False
@@ -271,6 +283,8 @@ class TrainModel(nn.Module):
 
     def calc_score(self, embedding, triplets):
         node_emb = embedding[0] if isinstance(embedding, (tuple, list)) else embedding
+        if not node_emb.is_cuda:                               # (CPU: the reference's indexing)
+            return torch.sum(node_emb[triplets[:, 0]] * self.w_relation[triplets[:, 1]] * node_emb[triplets[:, 2]], dim=1)
         # model.py:669-677; the two endpoint lookups as ONE row gather whose backward is a segment sum
         so = ops.take_rows(node_emb, torch.cat([triplets[:, 0], triplets[:, 2]]), key=triplets, tag="subject|object")
         s, o = so[:triplets.size(0)], so[triplets.size(0):]
@@ -298,8 +312,11 @@ class TrainModel(nn.Module):
                 continue
             reg = reg + torch.mean(emb.pow(2))
         if edge_type is not None:
-            for emb in embs:
-                if emb.size(0) == edge_type.size(0):
+            for k, emb in enumerate(embs):
+                # a padded graph: the edge representation by POSITION (the entry 1 of a tuple; a single node tensor never) --
+                # its capacities can collide (ncap == ecap) where the real counts do not; a step whose real N == E runs
+                # unpadded (unc_harness.SampledStep), where the reference's row-count rule below applies as it is
+                if (k == 1 and len(embs) > 1) if valid is not None else emb.size(0) == edge_type.size(0):
                     # model.py:703-707 selects the rows with ``emb[mask]`` (a host sync for the row count and a
                     # serialised indexing backward); same mean as a mask-weighted sum over all rows
                     num_rels = self.w_relation.size(0)
@@ -317,6 +334,10 @@ class TrainModel(nn.Module):
                     mask, clamped = cached[1], cached[2]
                     if valid is not None:
                         mask = mask * valid.edge_mask
+                    if not emb.is_cuda:                        # (CPU: the reference's indexing)
+                        emb_diff = self.edge_fc(emb) - self.w_relation[clamped]
+                        reg = reg + (torch.pow(emb_diff, 2) * mask).sum() / (mask.sum() * emb_diff.size(1))
+                        continue
                     emb_diff = self.edge_fc(emb) - ops.take_rows_small_table(self.w_relation, clamped)
                     reg = reg + (torch.pow(emb_diff, 2) * mask).sum() / (mask.sum() * emb_diff.size(1))
         return reg

@@ -123,7 +123,23 @@ class SampledStep:
         self.optimizer.step()
         return loss.detach()
 
+    def eager(self, sub, edge_type, samples, labels):
+        """The same step on the sub-graph itself, unpadded and not recorded."""
+        self.sync.detach_grads()
+        embed, _ = self.model(sub, sub.ndata[SUBGRAPH_NID], edge_type, sub.edata["norm"])
+        loss = self.model.get_unsupervised_loss(sub, embed, edge_type, samples, labels)
+        loss.backward()
+        self.sync.pack()
+        if self.grad_norm and self.grad_norm > 0:
+            torch.nn.utils.clip_grad_norm_([self.sync.master], self.grad_norm)
+        self.optimizer.step()
+        return loss.detach()
+
     def __call__(self, sub, edge_type, samples, labels):
+        if sub.number_of_nodes() == sub.number_of_edges():
+            # the regulariser's edge term takes every representation with one row per edge (model.py:700-707): with N == E the
+            # node representation too -- a rule of the real counts, which the padded step cannot see: run this one as it is
+            return self.eager(sub, edge_type, samples, labels)
         caps, arrays = pad_sampled(sub, edge_type, self.node_quantum, self.edge_quantum, int(self.model.model.num_nodes))
         return self.steps(caps, *arrays, samples, labels)
 
@@ -208,7 +224,10 @@ def collect_node_embeddings(model, graph, triplets, graph_batch_size=2000, sampl
                                       negative_sample, gen)
         nid = sub.ndata[SUBGRAPH_NID]
         coef = ((sub.in_degrees().float() + 1) / (full_in[nid] + 1)).view(-1, 1)
-        node_emb[nid] = node_emb[nid] * (1 - coef) + embed[0] * coef
+        # (the encoder's node representation: entry 0 of DMPNN's tuple, the tensor itself for R-GCN / R-GIN -- their
+        # reference drivers blend ``embed[0]``, row 0 of that tensor, into every node: DESIGN.md §8)
+        node_out = embed[0] if isinstance(embed, (tuple, list)) else embed
+        node_emb[nid] = node_emb[nid] * (1 - coef) + node_out * coef
         covered[nid] = True
     return node_emb, covered
 

@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 89
+#define DMP_ABI_VERSION 90
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1445,6 +1445,23 @@ int dmp_rnn_fwd(const float *P, const float *Whh, const float *bhn, const float 
  * r z n and W_hn h + b_hn; RNN 1) from dY [B, L, D Hd] at Y (times gate if given) and the forward's H and S. */
 int dmp_rnn_bwd(const float *dY, const float *gate, const float *Whh, const float *H, const float *S, int64_t B, int64_t L, int D,
                 int Hd, int cell, float *dG, void *stream);
+
+/* ---- Relational graph convolution of the UNC baselines (dmp_relconv.hip; DGL 0.6 RelGraphConv with the basis regulariser,
+ * UNC Model/R-GCN/src/model.py:117-147, Model/R-GIN/src/model.py:117-196), transform then aggregate.  Y [N, (R + loop) P] =
+ * x @ [W_0 | ... | W_{R-1} | loop_weight] (the caller's GEMM; every block padded to P columns, P % 4 == 0, the padding zero,
+ * Y 16-byte aligned).  Graph: the in-CSR (forward) and out-CSR (backward) of dmp_csr_build_pair, src32 / dst32, etype int64 [E],
+ * norm float [E] or NULL (1).  act: 0 none, 1 tanh.  Sums in ascending edge id, no atomics; an edge whose type is outside
+ * [0, R) contributes nothing.  DMP_ERR_UNSUPPORTED when R P floats exceed the backward's LDS (dmp_relconv_supported == 0). */
+int dmp_relconv_supported(int num_rels, int out_p);
+/* out [N, H] = act(sum_{e -> v} norm_e Y[src e, t_e] + bias + (loop ? Y[v, R] : 0));  bias [H] or NULL. */
+int dmp_relconv_fwd(const float *Y, const int32_t *in_ptr, const int32_t *in_ent, const int32_t *src32, const int64_t *etype,
+                    const float *norm, const float *bias, int64_t N, int R, int loop, int H, int P, int act, float *out,
+                    void *stream);
+/* g = dOut [N, H] * act'(out);  dY [N, (R + loop) P]:  dY[u, r] = sum_{e: u ->, t_e = r} norm_e g[dst e],  dY[u, R] = g[u]
+ * (loop), padding columns zero.  out: the forward's output (needed for tanh only). */
+int dmp_relconv_bwd(const float *dOut, const float *out, const int32_t *out_ptr, const int32_t *out_ent, const int32_t *dst32,
+                    const int64_t *etype, const float *norm, int64_t N, int R, int loop, int H, int P, int act, float *dY,
+                    void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,281 @@
+"""R-GCN / R-GIN's relational conv on ``dmp_relconv_fwd`` / ``dmp_relconv_bwd`` (unc_rel.RelGraphConv): against an fp64
+restatement of DGL 0.6's per-edge arithmetic at widths 50, 64 and 256 with up to 20 relation types, zero-in-degree nodes,
+a hub of more than 1,000 in-edges and the empty graph, every gradient (w_comp included), bitwise repeatable; against the
+reference's fixtures; the padded sampled step against the step on the sub-graph itself; replayed training against the
+eager loop, also on a sub-graph whose padded capacities collide; both encoders learn the two-community link structure."""
+import copy
+
+import numpy as np
+import pytest
+import torch as th
+
+pytestmark = pytest.mark.gpu
+
+
+def _graph(N, E, R, hub_in, seed, device):
+    """Random edges among the first N - 8 nodes (the last 8 have no in-edge); node 1 receives ``hub_in`` more."""
+    gen = th.Generator().manual_seed(seed)
+    src = th.randint(0, N, (E + hub_in,), generator=gen)
+    dst = th.cat([th.randint(0, max(1, N - 8), (E,), generator=gen), th.full((hub_in,), 1, dtype=th.int64)])
+    perm = th.randperm(E + hub_in, generator=gen)
+    src, dst = src[perm], dst[perm]
+    et = th.randint(0, R, (E + hub_in,), generator=gen)
+    norm = th.rand(E + hub_in, 1, generator=gen) + 0.1
+    return src.to(device), dst.to(device), et.to(device), norm.to(device)
+
+
+def _fp64_layer(m, x, src, dst, et, norm, act):
+    """DGL 0.6's RelGraphConv in float64 on the CPU: per-edge x[src] @ W[type], times norm, summed by destination."""
+    p = {k: v.detach().cpu().double().requires_grad_(True) for k, v in m.named_parameters()}
+    xd = x.detach().cpu().double().requires_grad_(True)
+    s, d, t = src.cpu(), dst.cpu(), et.cpu()
+    if "w_comp" in p:
+        W = (p["w_comp"] @ p["weight"].view(m.num_bases, -1)).view(m.num_rels, m.in_feat, m.out_feat)
+    else:
+        W = p["weight"]
+    msg = th.bmm(xd[s].unsqueeze(1), W[t]).squeeze(1)
+    if norm is not None:
+        msg = msg * norm.cpu().double()
+    out = th.zeros(x.size(0), m.out_feat, dtype=th.float64).index_add(0, d, msg) + p["h_bias"] + xd @ p["loop_weight"]
+    if act:
+        out = th.tanh(out)
+    return out, xd, p
+
+
+def _close(a, b, tol, what):
+    a, b = a.detach().cpu().double(), b.detach().cpu().double()
+    scale = max(1.0, float(b.abs().max())) if b.numel() else 1.0
+    err = float((a - b).abs().max()) if b.numel() else 0.0
+    assert err <= tol * scale, "%s: %g (scale %g)" % (what, err, scale)
+
+
+def _spy(monkeypatch):
+    from dualmessagepassing_amd import unc_rel
+    calls = []
+    real = unc_rel._RelAgg.apply
+    monkeypatch.setattr(unc_rel._RelAgg, "apply", lambda *a: (calls.append(1), real(*a))[1])
+    return calls
+
+
+@pytest.mark.parametrize("width,R,bases,with_norm,act", [
+    (50, 8, None, True, True), (50, 20, 4, False, False), (64, 2, None, True, False), (64, 20, None, False, True),
+    (256, 8, 3, True, True), (256, 20, None, True, False), (7, 3, None, True, True)])
+def test_relconv_matches_fp64_and_is_repeatable(width, R, bases, with_norm, act, gpu, monkeypatch):
+    from dualmessagepassing_amd.graph import BatchedGraph
+    from dualmessagepassing_amd.unc_rel import RelGraphConv
+    calls = _spy(monkeypatch)
+    th.manual_seed(width + R)
+    N, E, din = 700, 3000, 48
+    src, dst, et, norm = _graph(N, E, R, 1200, width * 31 + R, gpu)
+    m = RelGraphConv(din, width, R, num_bases=bases, activation=th.nn.Tanh() if act else None).to(gpu)
+    with th.no_grad():
+        m.h_bias.uniform_(-0.2, 0.2)
+    x = th.randn(N, din, device=gpu)
+    w_out = th.randn(N, width, device=gpu)
+
+    def run():
+        g = BatchedGraph(src, dst, N)
+        xg = x.clone().requires_grad_(True)
+        m.zero_grad(set_to_none=True)
+        out = m(g, xg, et, norm if with_norm else None)
+        (out * w_out).sum().backward()
+        return out.detach(), xg.grad, {k: v.grad.clone() for k, v in m.named_parameters()}
+
+    out, dx, grads = run()
+    assert calls, "the HIP path was not taken"
+    ref, xd, p = _fp64_layer(m, x, src, dst, et, norm if with_norm else None, act)
+    (ref * w_out.cpu().double()).sum().backward()
+    _close(out, ref, 2e-5, "out")
+    _close(dx, xd.grad, 1e-4, "dx")
+    for k, gk in grads.items():
+        _close(gk, p[k].grad, 2e-4, "grad " + k)
+    assert int((th.bincount(dst, minlength=N)[N - 8:] != 0).sum()) == 0 and int((dst == 1).sum()) > 1000
+    out2, dx2, grads2 = run()                                      # bitwise repeatable
+    assert th.equal(out, out2) and th.equal(dx, dx2)
+    for k in grads:
+        assert th.equal(grads[k], grads2[k]), k
+
+
+def test_relconv_on_the_empty_graph(gpu, monkeypatch):
+    from dualmessagepassing_amd.graph import BatchedGraph
+    from dualmessagepassing_amd.unc_rel import RelGraphConv
+    calls = _spy(monkeypatch)
+    th.manual_seed(0)
+    m = RelGraphConv(16, 50, 4, activation=th.nn.Tanh()).to(gpu)
+    x = th.randn(10, 16, device=gpu, requires_grad=True)
+    e = th.zeros(0, dtype=th.int64, device=gpu)
+    out = m(BatchedGraph(e, e, 10), x, e, th.zeros(0, 1, device=gpu))
+    out.sum().backward()
+    assert calls
+    ref = th.tanh(x.detach() @ m.loop_weight.detach() + m.h_bias.detach())
+    _close(out, ref, 1e-5, "out")
+    assert float(m.weight.grad.abs().max()) == 0.0 and float(m.loop_weight.grad.abs().max()) > 0.0
+
+
+@pytest.mark.parametrize("tag", __import__("test_unc_rel_cpu").CASES)
+def test_hip_path_matches_the_reference_fixtures(tag, gpu, monkeypatch):
+    from test_unc_rel_cpu import close, load_case, run_case
+    calls = _spy(monkeypatch)
+    d = load_case(tag)
+    model, outs, embed, loss = run_case(d, gpu)
+    assert len(calls) == int(d["layers"])
+    for i, o in enumerate(outs):
+        close(o, d["out.layer%d" % i], 2e-5, "%s layer %d" % (tag, i))
+    close(loss.view(()), d["loss"], 2e-5, tag + " loss")
+    for k, p in model.named_parameters():
+        if p.grad is not None:
+            close(p.grad, d["grad." + k], 5e-4, "%s grad %s" % (tag, k))
+
+
+def _two_communities(rng, n, m=1500):
+    half = n // 2
+    u = rng.integers(0, n, 4 * m)
+    v = rng.integers(0, n, 4 * m)
+    same = (u < half) == (v < half)
+    keep = (u != v) & (same | (rng.random(4 * m) < 0.03))
+    pairs = np.unique(np.stack([u[keep], v[keep]], 1), axis=0)[:m]
+    return np.stack([pairs[:, 0], rng.integers(0, 3, len(pairs)), pairs[:, 1]], 1)
+
+
+@pytest.mark.parametrize("encoder", ["RGCN", "RGIN"])
+def test_padded_step_equals_the_step_on_the_sub_graph(encoder, gpu):
+    from dualmessagepassing_amd.graph import BatchedGraph
+    from dualmessagepassing_amd.unc import PaddedRows, TrainModel
+    from dualmessagepassing_amd.unc_harness import graph_of, pad_sampled
+    from dualmessagepassing_amd.unc_sampling import generate_sampled_graph_and_labels_unsupervised
+    rng = np.random.default_rng(3)
+    n = 600
+    graph, trip = graph_of(_two_communities(rng, n), n, 3, gpu)
+    th.manual_seed(0)
+    model = TrainModel(None, n, 50, 3, 0, num_hidden_layers=2, dropout=0.0, reg_param=0.01, encoder=encoder).to(gpu)
+    twin = copy.deepcopy(model)
+    gen = th.Generator(device=gpu).manual_seed(5)
+    sub, samples, labels = generate_sampled_graph_and_labels_unsupervised(graph, trip[:256], 2, 8, 0.5, 3, generator=gen, sampler="neighbor")
+    et = sub.edata["type"]
+    emb, _ = model(sub, sub.ndata["_ID"], et, sub.edata["norm"])
+    loss = model.get_unsupervised_loss(sub, emb, et, samples, labels)
+    loss.backward()
+    (ncap, ecap), (src, dst, etp, norm, nid, counts) = pad_sampled(sub, et, 512, 2048, n)
+    g = BatchedGraph(src, dst, ncap)
+    g._dmp_valid = PaddedRows(counts[0:1], counts[1:2], ncap, ecap)
+    g.edata["type"], g.edata["norm"] = etp, norm
+    emb2, _ = twin(g, nid, etp, norm)
+    loss2 = twin.get_unsupervised_loss(g, emb2, etp, samples, labels)
+    loss2.backward()
+    N = sub.number_of_nodes()
+    assert abs(float(loss2.detach()) - float(loss.detach())) <= 2e-6 * max(1.0, abs(float(loss)))
+    _close(emb2[:N], emb, 2e-5, "node rows")
+    for (name, p), q in zip(model.named_parameters(), twin.parameters()):
+        assert (p.grad is None) == (q.grad is None), name
+        if p.grad is not None:
+            _close(q.grad, p.grad, 1e-4, name)
+
+
+def _train_pair(encoder, gpu, n=900, **over):
+    from dualmessagepassing_amd import unc_harness
+    from dualmessagepassing_amd.unc import TrainModel
+    rng = np.random.default_rng(11)
+    graph, trip = unc_harness.graph_of(_two_communities(rng, n), n, 3, gpu)
+    th.manual_seed(0)
+    model = TrainModel(None, n, 50, 3, 0, num_hidden_layers=2, dropout=0.0, reg_param=0.01, encoder=encoder).to(gpu)
+    twin = copy.deepcopy(model)
+    kw = dict(n_epochs=3, graph_batch_size=300, lr=5e-3, sampler="neighbor", sample_depth=2, sample_width=8, negative_sample=3,
+              rescale_epochs=False, seed=1)
+    kw.update(over)
+    ref = unc_harness.train_unsupervised(model, graph, trip, **kw)
+    made = []
+    real = unc_harness.SampledStep
+    unc_harness.SampledStep = lambda *a, **k: (made.append(real(*a, **k)), made[-1])[1]
+    try:
+        got = unc_harness.train_unsupervised(twin, graph, trip, replay=True, **kw)
+    finally:
+        unc_harness.SampledStep = real
+    return ref, got, made[0].steps
+
+
+@pytest.mark.parametrize("encoder", ["RGCN", "RGIN"])
+def test_replayed_training_follows_the_eager_loss_curve(encoder, gpu):
+    ref, got, sg = _train_pair(encoder, gpu)
+    assert len(got) == len(ref)
+    for a, b in zip(got, ref):
+        assert abs(a - b) <= 1e-3 * max(1.0, abs(b)), (got, ref)
+    assert sg.replays >= 0.5 * (sg.replays + sg.eager_calls), (sg.replays, sg.eager_calls)
+
+
+def _sub_graph(N, E, num_rels, device, seed):
+    from dualmessagepassing_amd.graph import BatchedGraph
+    from dualmessagepassing_amd.unc import compute_edgenorm
+    gen = th.Generator().manual_seed(seed)
+    src, dst = th.randint(0, N, (E,), generator=gen).to(device), th.randint(0, N, (E,), generator=gen).to(device)
+    sub = BatchedGraph(src, dst, N)
+    sub.ndata["_ID"] = th.randperm(N, generator=gen).to(device)
+    sub.edata["type"] = th.randint(0, 2 * num_rels, (E,), generator=gen).to(device)
+    sub.edata["norm"] = compute_edgenorm(sub)
+    S = 1200
+    samples = th.stack([th.randint(0, N, (S,), generator=gen), th.randint(0, num_rels, (S,), generator=gen),
+                        th.randint(0, N, (S,), generator=gen)], 1).to(device)
+    labels = (th.rand(S, generator=gen) < 0.3).float().to(device)
+    return sub, samples, labels
+
+
+@pytest.mark.parametrize("encoder", ["RGCN", "RGIN", "DMPNN"])
+def test_replayed_steps_on_colliding_capacities_follow_the_eager_steps(encoder, gpu):
+    """A sub-graph of 1,600 nodes and 2,000 edges: both padded capacities are 2048.  Four steps through ``SampledStep``
+    (recorded, then replayed) against the same four steps taken eagerly on the sub-graph itself; and a sub-graph with as many
+    nodes as edges, which ``SampledStep`` runs unpadded."""
+    from dualmessagepassing_amd.dp import FlatAdamW, FlatGradSync
+    from dualmessagepassing_amd.unc import TrainModel
+    from dualmessagepassing_amd.unc_harness import SampledStep, pad_sampled
+    num_rels = 3
+    th.manual_seed(0)
+    model = TrainModel(None, 1700, 64, num_rels, 0, num_hidden_layers=2, dropout=0.0, reg_param=0.5, encoder=encoder).to(gpu)
+    twin = copy.deepcopy(model)
+    subs = [_sub_graph(1600, 2000, num_rels, gpu, s) for s in range(3)] + [_sub_graph(1500, 1500, num_rels, gpu, 9)]
+    assert pad_sampled(subs[0][0], subs[0][0].edata["type"], parent_nodes=1700)[0] == (2048, 2048)
+
+    def steppers(m, capturable):
+        sync = FlatGradSync(m)
+        master = sync.flatten_parameters()
+        opt = FlatAdamW([master], lr=1e-3, weight_decay=0.0, capturable=capturable)
+        return SampledStep(m, sync, opt, 1.0)
+
+    eager, padded = steppers(model, True), steppers(twin, True)
+    want, got = [], []
+    for sub, samples, labels in subs:
+        want.append(float(eager.eager(sub, sub.edata["type"], samples, labels)))
+    with padded.steps.on_stream():
+        for sub, samples, labels in subs:
+            got.append(float(padded(sub, sub.edata["type"], samples, labels)))
+    for a, b in zip(got, want):
+        assert abs(a - b) <= 1e-4 * max(1.0, abs(b)), (got, want)
+    assert padded.steps.replays >= 1, (padded.steps.replays, padded.steps.eager_calls)
+
+
+@pytest.mark.parametrize("encoder", ["RGCN", "RGIN"])
+def test_both_encoders_learn_the_link_structure(encoder, gpu):
+    from dualmessagepassing_amd.unc import TrainModel
+    from dualmessagepassing_amd.unc_harness import collect_node_embeddings, graph_of, train_unsupervised
+    rng = np.random.default_rng(7)
+    n = 240
+    half = n // 2
+    u, v = rng.integers(0, n, 6000), rng.integers(0, n, 6000)
+    keep = (u != v) & (((u < half) == (v < half)) | (rng.random(6000) < 0.03))
+    pairs = np.unique(np.stack([u[keep], v[keep]], 1), axis=0)[:1500]
+    trip_np = np.stack([pairs[:, 0], np.zeros(len(pairs), np.int64), pairs[:, 1]], 1)
+    graph, trip = graph_of(trip_np, n, 1, gpu)
+    th.manual_seed(0)
+    model = TrainModel(None, n, 64, 1, 0, num_hidden_layers=2, dropout=0.0, reg_param=0.01, encoder=encoder).to(gpu)
+    hist = train_unsupervised(model, graph, trip, n_epochs=6, graph_batch_size=300, lr=5e-3, sampler="neighbor", sample_depth=2,
+                              sample_width=8, negative_sample=3, rescale_epochs=False, seed=1)
+    assert np.isfinite(hist).all() and min(hist) < 0.9 * hist[0], hist
+    emb, covered = collect_node_embeddings(model, graph, trip, graph_batch_size=300, sampler="neighbor", sample_depth=2,
+                                           sample_width=8, negative_sample=3, seed=2)
+    assert emb.shape == (n, 64) and bool(th.isfinite(emb).all())
+    table = model.model.node_emb.weight.detach()
+    assert bool(covered.any()) and not th.equal(emb[covered], table[covered])       # the encoder's rows, not row 0 or the table
+    with th.no_grad():
+        model.eval()
+        fake = th.stack([th.randint(0, n, (trip.size(0),), device=gpu), th.zeros(trip.size(0), dtype=th.int64, device=gpu),
+                         th.randint(0, n, (trip.size(0),), device=gpu)], 1)
+        pos, neg = model.calc_score(emb, trip), model.calc_score(emb, fake)
+    assert float(pos.mean()) > float(neg.mean()) + 0.1, (float(pos.mean()), float(neg.mean()))
