@@ -13,8 +13,9 @@ uni- or bidirectional.  It reads the parameters of the layer's own torch module,
 
 The recurrence runs over all L positions, the pre-padding included, as the reference's module does.
 
-``hip_layer_ok`` decides: Hd (hidden size per direction) 32, 64 or 128, input width equal to the output width, fp32 on the
-GPU, dropout 0 or eval mode.  Anything else runs the layer's torch module (also the CPU path)."""
+``hip_layer_ok`` decides: Hd (hidden size per direction) 32, 64 or 128, any input width (it only shapes ``W_ih`` and the
+GEMMs around the recurrence; the residual is added when it equals the output width ``D Hd``, as ``forward_rows`` does),
+fp32 on the GPU, dropout 0 or eval mode.  Anything else runs the layer's torch module (also the CPU path)."""
 import torch as th
 
 CELLS = {"LSTM": (0, 4), "GRU": (1, 3), "RNN": (2, 1)}     # name -> (kernel code, gates per direction)

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch as th
 
+from util_fp64 import relconv_fp64 as _fp64_layer
+
 pytestmark = pytest.mark.gpu
 
 
@@ -22,24 +24,6 @@ def _graph(N, E, R, hub_in, seed, device):
     et = th.randint(0, R, (E + hub_in,), generator=gen)
     norm = th.rand(E + hub_in, 1, generator=gen) + 0.1
     return src.to(device), dst.to(device), et.to(device), norm.to(device)
-
-
-def _fp64_layer(m, x, src, dst, et, norm, act):
-    """DGL 0.6's RelGraphConv in float64 on the CPU: per-edge x[src] @ W[type], times norm, summed by destination."""
-    p = {k: v.detach().cpu().double().requires_grad_(True) for k, v in m.named_parameters()}
-    xd = x.detach().cpu().double().requires_grad_(True)
-    s, d, t = src.cpu(), dst.cpu(), et.cpu()
-    if "w_comp" in p:
-        W = (p["w_comp"] @ p["weight"].view(m.num_bases, -1)).view(m.num_rels, m.in_feat, m.out_feat)
-    else:
-        W = p["weight"]
-    msg = th.bmm(xd[s].unsqueeze(1), W[t]).squeeze(1)
-    if norm is not None:
-        msg = msg * norm.cpu().double()
-    out = th.zeros(x.size(0), m.out_feat, dtype=th.float64).index_add(0, d, msg) + p["h_bias"] + xd @ p["loop_weight"]
-    if act:
-        out = th.tanh(out)
-    return out, xd, p
 
 
 def _close(a, b, tol, what):
