@@ -8,225 +8,10 @@ import os
 import threading
 
 from . import _build
+# The declarations live in _abi.py: tests/test_lib_abi.py parses include/dmp_hip.h and compares every signature, struct
+# field and limit there with it.
+from ._abi import ABI_VERSION, SIGNATURES
 
-c_i64 = ctypes.c_int64
-c_double = ctypes.c_double
-c_int = ctypes.c_int
-c_f32 = ctypes.c_float
-c_ptr = ctypes.c_void_p
-c_size = ctypes.c_size_t
-
-# name -> (restype, argtypes); mirrors include/dmp_hip.h one to one.
-SIGNATURES = {
-    "dmp_abi_version": (c_int, []),
-    "dmp_last_hip_error": (ctypes.c_char_p, []),
-    "dmp_csr_workspace_words": (c_size, [c_i64, c_i64]),
-    "dmp_csr_build": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_incidence_build": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
-    "dmp_degree_coef": (c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_collate": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
-                            c_ptr, c_ptr, c_ptr]),
-    "dmp_add_reversed_edges": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64,
-                                       c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_line_graph_count": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_line_graph_fill": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_first_edge_of_id": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "dmp_dedupe_table_words": (c_size, [c_i64]),
-    "dmp_dedupe_first": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
-    "dmp_subiso_node_weights": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_dual_subisomorphisms": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
-                                         c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_subiso_enumerate": (c_i64, [c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
-                                     c_i64]),
-    "dmp_subiso_count_batch": (c_int, [c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                       c_ptr, c_int]),
-    "dmp_random_walks": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, ctypes.c_uint64, c_ptr, c_ptr, c_ptr]),
-    "dmp_sample_in_edges": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, ctypes.c_uint64, c_ptr, c_ptr]),
-    "dmp_pool_index": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                               c_ptr, c_ptr]),
-    "dmp_pattern_edge_active": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_subiso_edge_weights": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                        c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "dmp_class_tiles_workspace_words": (c_size, [c_i64, c_int]),
-    "dmp_class_tiles": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_csr_keep_scratch_words": (c_i64, [c_i64]),
-    "dmp_csr_keep": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_class_tiles_gated": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_scan_workspace_words": (c_size, [c_i64]),
-    "dmp_exclusive_scan_i64": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
-    "dmp_seg_sum": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr]),
-    "dmp_seg_sum2": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_f32, c_ptr, c_i64,
-                             c_int, c_ptr]),
-    "dmp_small_gemm_jobs": (c_int, [c_ptr, c_int, c_ptr]),
-    "dmp_pool_index_jobs": (c_int, [c_ptr, c_int, c_ptr]),
-    "dmp_collate_jobs": (c_int, [c_ptr, c_int, c_ptr]),
-    "dmp_csr_build_graphs_max_nodes": (c_int, []),
-    "dmp_csr_build_graphs": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                     c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_pool_weight_sums": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_gate_compact_hist_nodes": (c_int, []),
-    "dmp_gate_compact": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
-                                 c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_out_degrees": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "dmp_seg_sum2_graphs_max_nodes": (c_int, []),
-    "dmp_seg_sum2_graphs": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_f32,
-                                    c_ptr, c_i64, c_ptr]),
-    "dmp_seg_sum2_graphs_masked": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_f32,
-                                           c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
-    "dmp_seg_sum2_rows": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_f32, c_f32, c_ptr, c_i64, c_ptr]),
-    "dmp_incidence_keep": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_seg_sum2_tiled": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_f32,
-                                   c_ptr, c_i64, c_ptr]),
-    "dmp_gather_rows": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr]),
-    "dmp_gather_select": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_f32,
-                                  c_ptr, c_i64, c_ptr]),
-    "dmp_colsum_partial_rows": (c_i64, [c_i64, c_int]),
-    "dmp_gate_residual": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr]),
-    "dmp_scale_rows_colsum": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_relu_bwd_colsum": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_edge_combine_bwd_g_colsum": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_colsum_partials": (c_int, [c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr]),
-    "dmp_reduce_partials": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr]),
-    "dmp_add_bias_relu": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_f32, c_ptr, c_i64, c_ptr]),
-    "dmp_heads_forward": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_f32, c_ptr]),
-    "dmp_heads_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_f32, c_ptr]),
-    "dmp_fold_layers": (c_int, [c_ptr, c_ptr, c_int, c_int, c_ptr]),
-    "dmp_unfold_layers": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr]),
-    "dmp_smallk_embed_gate": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr]),
-    "dmp_smallk_embed_live": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr]),
-    "dmp_smallk_atb_blocks": (c_i64, [c_i64]),
-    "dmp_smallk_embed_cols": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr]),
-    "dmp_smallk_atb_cols_masked": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "dmp_smallk_atb_cols_rows": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "dmp_smallk_atb": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "dmp_smallk_atb_jobs": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr]),
-    "dmp_l0_pack_jobs": (c_int, [c_ptr, c_int, c_ptr]),
-    "dmp_count_loss": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_f32, c_ptr, c_ptr, c_ptr]),
-    "dmp_reduce_partials_multi": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr]),
-    "dmp_l0_pack": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "dmp_l0_edge_fwd_masked": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
-                                       c_f32, c_ptr, c_i64, c_ptr]),
-    "dmp_l0_bwd_w_blocks": (c_i64, [c_i64]),
-    "dmp_l0_node_pack_rows": (c_i64, []),
-    "dmp_l0_node_fwd": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr, c_f32, c_ptr,
-                                c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
-    "dmp_bn_partial_rows": (c_i64, [c_i64, c_int]),
-    "dmp_bn_train_fwd": (c_int, [c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_int, c_f32, c_ptr, c_ptr, c_ptr,
-                                 c_i64, c_ptr]),
-    "dmp_bn_train_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_ptr, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_i64,
-                                 c_ptr]),
-    "dmp_bn_train_fwd_rows": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_int, c_f32, c_ptr, c_ptr,
-                                      c_ptr, c_i64, c_ptr]),
-    "dmp_bn_train_bwd_rows": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_int, c_ptr, c_int, c_f32, c_ptr, c_ptr, c_ptr,
-                                      c_i64, c_ptr]),
-    "dmp_l0_bwd_w_masked": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "dmp_scalar_filter_gates": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_i64, c_ptr]),
-    "dmp_csr_pair_workspace_words": (ctypes.c_size_t, [c_i64]),
-    "dmp_csr_build_pair": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                   c_ptr, c_ptr]),
-    "dmp_heads_blend": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr]),
-    "dmp_concat_pairs": (c_int, [c_ptr, c_int, c_ptr]),
-    "dmp_table_rows": (c_int, [c_ptr, c_int, c_ptr]),
-    "dmp_len_masks": (c_int, [c_ptr, c_int, c_i64, c_ptr]),
-    "dmp_pack_segments": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr]),
-    "dmp_adamw_step": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_double, c_double, c_double, c_double,
-                               c_double, c_i64, c_ptr]),
-    "dmp_adamw_step_skip": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_double, c_double, c_double, c_double,
-                                    c_double, c_i64, c_ptr, c_ptr, c_int, c_ptr]),
-    "dmp_adamw_step_dev": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_double, c_double, c_double, c_double,
-                                   c_ptr, c_ptr, c_int, c_ptr]),
-    "dmp_adamw_step_segments": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_double, c_double,
-                                        c_double, c_double, c_ptr, c_int, c_ptr]),
-    "dmp_adamw_step_guarded": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_double, c_double, c_double, c_double,
-                                       c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr]),
-    "dmp_edge_select_build": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_edge_select_nodes": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_edge_fwd_fused": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
-                                   c_i64, c_int, c_f32, c_ptr, c_i64, c_ptr]),
-    "dmp_edge_fwd_typed": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                   c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64, c_ptr]),
-    "dmp_bwd_z_typed_arow": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_f32,
-                                     c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
-    "dmp_mask_slots": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_pool_relu_bwd_blocks": (c_i64, [c_i64, c_int]),
-    "dmp_pool_relu_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64,
-                                  c_ptr, c_ptr, c_ptr]),
-    "dmp_relu_bwd_gathered_colsum": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_dev_set_exact_fp32": (None, [c_int]),
-    "dmp_dev_get_exact_fp32": (c_int, []),
-    "dmp_rel_gemm": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64,
-                             c_int, c_ptr, c_i64, c_ptr]),
-    "dmp_rel_atb_blocks": (c_i64, [c_int]),
-    "dmp_rel_atb": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr]),
-    "dmp_atb_typed_blocks_h": (c_i64, [c_i64, c_int]),
-    "dmp_atb_rows_blocks_h": (c_i64, [c_i64, c_int, c_int, c_int]),
-    "dmp_atb_rows_plain": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "dmp_atb_rows_masked": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    "dmp_atb_jobs_blocks_h": (c_i64, [c_i64, c_int, c_int]),
-    "dmp_atb_rows_jobs_h": (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
-    "dmp_atb_tile_jobs_blocks": (c_i64, [c_i64, c_int, c_int]),
-    "dmp_mfma_partial_rows_h": (c_i64, [c_i64, c_int]),
-    "dmp_gemm_k64": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_i64, c_ptr]),
-    "dmp_atb_typed": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
-    "dmp_out_fwd_fused_rows": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr,
-                                       c_i64, c_ptr]),
-    "dmp_bwd_h1_fused_rows": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_f32, c_ptr,
-                                      c_i64, c_ptr, c_ptr, c_ptr]),
-    "dmp_kept_rows_scratch_words": (c_i64, [c_i64]),
-    "dmp_kept_rows": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_l0_edge_fwd_rows": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
-                                     c_f32, c_ptr, c_i64, c_ptr]),
-    "dmp_l0_bwd_w_rows": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "dmp_typed_partial_rows": (c_i64, [c_i64, c_int]),
-    "dmp_out_fwd_typed": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr]),
-    "dmp_bwd_h1_typed": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64,
-                                 c_ptr, c_ptr, c_ptr]),
-    "dmp_kept_rows_jobs": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_row_mask_bits_jobs": (c_int, [c_ptr, c_int, c_ptr]),
-    "dmp_atb2_blocks": (c_i64, [c_i64, c_int]),
-    "dmp_atb2_jobs": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr]),
-    "dmp_bwd_z_w": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_f32, c_f32,
-                            c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_out_fwd_typed_codes": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr]),
-    "dmp_bwd_h1_w_blocks": (c_i64, [c_i64]),
-    "dmp_bwd_h1_w": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64,
-                             c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_row_mask_bits": (c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
-    "dmp_row_mask_rows": (c_int, [c_ptr, c_i64, c_int, c_i64, c_ptr, c_ptr]),
-    "dmp_bwd_z_fused": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
-                                c_f32, c_f32, c_i64, c_int, c_ptr, c_i64, c_ptr]),
-    "dmp_gemm_k128": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_i64, c_int, c_ptr]),
-    "dmp_edge_combine": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
-                                 c_int, c_int, c_f32, c_ptr, c_i64, c_ptr]),
-    "dmp_relu_bwd_g_colsum": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_f32, c_ptr, c_i64,
-                                      c_ptr, c_ptr]),
-    "dmp_edge_combine_bwd_g": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr]),
-    "dmp_compgcn_agg": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int,
-                                c_ptr, c_i64, c_ptr]),
-    "dmp_compgcn_agg_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
-                                    c_i64, c_int, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
-    "dmp_attn_supported_dh": (c_int, [c_int]),
-    "dmp_attn_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_attn_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_f32, c_ptr,
-                             c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_mem_init_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr,
-                                 c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_mem_init_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    "dmp_cnn_fwd": (c_int, [c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_f32, c_ptr, c_int, c_ptr,
-                            c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_cnn_route_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_ptr, c_ptr]),
-    "dmp_cnn_wgrad_chunks": (c_i64, [c_i64]),
-    "dmp_cnn_wgrad": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "dmp_rnn_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "dmp_rnn_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "dmp_relconv_supported": (c_int, [c_int, c_int]),
-    "dmp_relconv_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr,
-                                c_ptr]),
-    "dmp_relconv_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr,
-                                c_ptr]),
-}
-
-ABI_VERSION = 90
 # ``_lib.VALIDATE = True``: index builds read back the kernels' status word (one host sync each) and raise on an edge endpoint
 # or a lookup index outside its range -- otherwise such an entry is dropped from the CSR and gathers read row 0 (validate
 # datasets once with harness.validate_samples, or run a debugging pass with this attribute set)

@@ -119,29 +119,16 @@ def scalar_filter_gate(p_pad, p_label, g_pad, g_label, num_labels):
     return present.index_select(0, g_pad.seg.long() * L + g_label.view(-1)).view(-1, 1)
 
 
-_FILTER_JOB = None
-
-
 def scalar_filter_gates(jobs):
     """``scalar_filter_gate`` for several element kinds at once -- ``jobs`` = list of ``(p_pad, p_label, g_pad, g_label,
     num_labels)`` -- as float ``[rows, 1]`` gates.  Device tensors: three dispatches for all jobs together
     (csrc/dmp_graph.hip::dmp_scalar_filter_gates) instead of nine small torch launches per kind."""
-    global _FILTER_JOB
-    import ctypes
-    from . import _lib
+    from . import _abi, _lib
     lib = _lib.load()
     _lib.require_gpu(*[t for j in jobs for t in (j[1], j[3])])   # no host implementation: device tensors only
-    if _FILTER_JOB is None:
-        class _Job(ctypes.Structure):
-            _fields_ = [("p_seg", ctypes.c_void_p), ("p_label", ctypes.c_void_p), ("num_p", ctypes.c_int64),
-                        ("p_sizes", ctypes.c_void_p), ("p_max", ctypes.c_int64),
-                        ("g_seg", ctypes.c_void_p), ("g_label", ctypes.c_void_p), ("num_g", ctypes.c_int64),
-                        ("num_labels", ctypes.c_int64), ("present_off", ctypes.c_int64), ("gate", ctypes.c_void_p),
-                        ("seg_is_i32", ctypes.c_int64)]
-        _FILTER_JOB = _Job
     dev = jobs[0][1].device
     B = jobs[0][0].bsz
-    J, keep, off, gates = (_FILTER_JOB * len(jobs))(), [], 0, []
+    J, keep, off, gates = (_abi.dmp_filter_job * len(jobs))(), [], 0, []
     for i, (p_pad, p_label, g_pad, g_label, L) in enumerate(jobs):
         if p_pad.bsz != B or g_pad.bsz != B:
             raise ValueError("filter jobs must cover the same pairs")
@@ -168,26 +155,16 @@ def scalar_filter_gates(jobs):
     return gates
 
 
-_MASK_JOB = None
-
-
 def len_masks(jobs):
     """Pre-padding masks ``[B, max, 1]`` (bool) and their row counts ``[B, 1]`` (float) for several element kinds --
     ``jobs`` = list of ``(padder, rev)`` with ``rev`` the per-row is-reversed flags or None (reversed edges leave
     the mask, basemodel.py:1521-1531).  Device tensors: ONE launch for all kinds (csrc/dmp_graph.hip::len_masks_k)
     instead of the arange / compare / masked_fill / sum chain per kind."""
-    global _MASK_JOB
-    import ctypes
-    from . import _lib
+    from . import _abi, _lib
     lib = _lib.load()
     _lib.require_gpu(*[p.sizes for p, _ in jobs])            # no host implementation: device tensors only
-    if _MASK_JOB is None:
-        class _Job(ctypes.Structure):
-            _fields_ = [("sizes", ctypes.c_void_p), ("off", ctypes.c_void_p), ("max_len", ctypes.c_int64),
-                        ("rev", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("count", ctypes.c_void_p)]
-        _MASK_JOB = _Job
     B, dev = jobs[0][0].bsz, jobs[0][0].sizes.device
-    J, keep, out = (_MASK_JOB * len(jobs))(), [], []
+    J, keep, out = (_abi.dmp_mask_job * len(jobs))(), [], []
     for i, (p, rev) in enumerate(jobs):
         if p.bsz != B:
             raise ValueError("mask jobs must cover the same graphs")

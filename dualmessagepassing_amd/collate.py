@@ -8,7 +8,7 @@ nodes of graphs 0..i-1, node/edge frames are concatenated, ``batch_num_nodes`` /
 """
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from ._lib import check, ptr, stream_ptr
 from .graph import BatchedGraph
 
@@ -55,28 +55,16 @@ def collate_device(local_src, local_dst, num_nodes, num_edges, total_nodes, tota
     return g
 
 
-_COLLATE_JOB = None
-
-
 def collate_device_many(batches):
     """``collate_device`` for several batches -- the pattern batch and the target batch of a step -- in ONE pair of launches
     (``dmp_collate_jobs``).  ``batches``: list of dicts with ``collate_device``'s arguments (``local_src``, ``local_dst``,
     ``num_nodes``, ``num_edges``, ``total_nodes``, ``total_edges`` and optionally ``ndata``, ``edata``, ``max_nodes``,
     ``max_edges``).  Returns the BatchedGraphs in order."""
-    global _COLLATE_JOB
-    import ctypes
     lib = _lib.load()
-    if _COLLATE_JOB is None:
-        P, I = ctypes.c_void_p, ctypes.c_int64
-
-        class _Job(ctypes.Structure):
-            _fields_ = [("local_src", P), ("local_dst", P), ("num_nodes", P), ("num_edges", P), ("B", I), ("N", I), ("E", I),
-                        ("node_off", P), ("edge_off", P), ("src", P), ("dst", P), ("edge_graph", P), ("node_graph", P)]
-        _COLLATE_JOB = _Job
-    if not 0 < len(batches) <= 4 or any(int(b["num_nodes"].numel()) == 0 or int(b["num_nodes"].numel()) > 2048 for b in batches):
+    if not 0 < len(batches) <= _abi.DMP_COLLATE_MAX_JOBS or any(int(b["num_nodes"].numel()) == 0 or int(b["num_nodes"].numel()) > 2048 for b in batches):
         return [collate_device(b["local_src"], b["local_dst"], b["num_nodes"], b["num_edges"], b["total_nodes"], b["total_edges"],
                                b.get("ndata"), b.get("edata"), True, b.get("max_nodes"), b.get("max_edges")) for b in batches]
-    J = (_COLLATE_JOB * len(batches))()
+    J = (_abi.dmp_collate_job * len(batches))()
     made, keep = [], []
     for k, b in enumerate(batches):
         ls, ld, nn, ne = b["local_src"], b["local_dst"], b["num_nodes"], b["num_edges"]
@@ -254,35 +242,23 @@ def batchify(samples, return_weights=None, device=None):
                                                        work_hint=hint)
 
 
-_CONCAT_JOB = None
-
-
 def concat_pairs(pairs):
     """``[cat([a, b + add]) for (a, b, add) in pairs]`` (1-D tensors; ``a`` may be ``(n, fill)`` for a constant fp32
     block; ``add`` only for int64).  Device tensors: ONE launch for all pairs (csrc/dmp_graph.hip::concat_pairs_k)."""
-    global _CONCAT_JOB
-    import ctypes
-    from . import _lib
 
     def plain(a, b, add):
         if isinstance(a, tuple):
             a = torch.full((a[0],), a[1], dtype=b.dtype, device=b.device)
         return torch.cat([a.reshape(-1), b.reshape(-1) + add if add else b.reshape(-1)])
 
-    ok = 0 < len(pairs) <= 12 and all(
+    ok = 0 < len(pairs) <= _abi.DMP_CONCAT_MAX_JOBS and all(
         b.is_cuda and b.element_size() in (1, 4, 8) and (not add or b.dtype == torch.int64)
         and ((isinstance(a, tuple) and b.dtype == torch.float32) or (torch.is_tensor(a) and a.is_cuda and a.dtype == b.dtype))
         for a, b, add in pairs)
     if not ok:
         return [plain(*p) for p in pairs]
     lib = _lib.load()
-    if _CONCAT_JOB is None:
-        class _Job(ctypes.Structure):
-            _fields_ = [("a", ctypes.c_void_p), ("na", ctypes.c_int64), ("b", ctypes.c_void_p), ("nb", ctypes.c_int64),
-                        ("out", ctypes.c_void_p), ("elem_size", ctypes.c_int), ("add_b", ctypes.c_int64),
-                        ("fill_a", ctypes.c_float)]
-        _CONCAT_JOB = _Job
-    J, keep, outs = (_CONCAT_JOB * len(pairs))(), [], []
+    J, keep, outs = (_abi.dmp_concat_job * len(pairs))(), [], []
     for k, (a, b, add) in enumerate(pairs):
         b = b.reshape(-1).contiguous()
         if isinstance(a, tuple):

@@ -364,7 +364,7 @@ class FlatAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        from . import _lib
+        from . import _abi, _lib
         loss = closure() if closure is not None else None
         lib = _lib.load()
         if self.veto is not None and sum(len(g["params"]) for g in self.param_groups) != 1:      # (add_param_group after set_veto)
@@ -386,7 +386,7 @@ class FlatAdamW(torch.optim.Optimizer):
                         st["max_exp_avg_sq"] = torch.zeros_like(p)
                 st["step"] += 1
                 seg = getattr(p, "_dmp_seg", None)
-                if seg is not None and seg[1] <= 1024 and seg[0].device == p.device:
+                if seg is not None and seg[1] <= _abi.DMP_ADAMW_MAX_SEGMENTS and seg[0].device == p.device:
                     # a flat buffer of parameter tensors: one step count per tensor (torch.optim.AdamW's state), on the device
                     import ctypes
                     dev, tab = self._segment_state(p, group, seg[1])
@@ -430,7 +430,7 @@ class FlatAdamW(torch.optim.Optimizer):
                     pos = off + n
                 if pos < p.numel():
                     gaps.append((pos, p.numel() // 4 * 4))
-                if len(gaps) <= 16:                          # DMP_ADAMW_MAX_SKIP: one launch
+                if len(gaps) <= _abi.DMP_ADAMW_MAX_SKIP:     # one launch
                     import ctypes
                     lo = (ctypes.c_int64 * max(len(gaps), 1))(*[g[0] for g in gaps])
                     hi = (ctypes.c_int64 * max(len(gaps), 1))(*[g[1] for g in gaps])

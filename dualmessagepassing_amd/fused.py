@@ -28,7 +28,7 @@ import threading
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib, ops
+from . import _abi, _lib, ops
 from ._lib import check, ptr, stream_ptr
 
 
@@ -37,7 +37,7 @@ def _partials(rows, H, dev):
     return torch.empty((int(lib.dmp_colsum_partial_rows(rows, H)), H), dtype=torch.float32, device=dev)
 
 
-MAX_REDUCE_SEGMENTS = 16   # DMP_REDUCE_MAX_SEGMENTS
+MAX_REDUCE_SEGMENTS = _abi.DMP_REDUCE_MAX_SEGMENTS
 
 
 class _Deferred(threading.local):
@@ -591,11 +591,6 @@ def bwd_z_w(d_pre, z, Wes, d_s, base, coef, index, WesT=None, base_map=None, gat
 USE_ATB2 = True     # the tile-list weight gradients on the bf16-piece LDS image (``dmp_atb2_jobs``)
 
 
-class _Atb2Job(_ctypes.Structure):
-    _fields_ = [("Z", _ctypes.c_void_p), ("ldz", _ctypes.c_int64), ("D", _ctypes.c_void_p), ("ldd", _ctypes.c_int64),
-                ("partial_T", _ctypes.c_void_p), ("partial_B", _ctypes.c_void_p), ("partial_stride", _ctypes.c_int64), ("ldp", _ctypes.c_int)]
-
-
 def atb2_ok(a, b, H):
     lib = _lib.load()
     lim = (1 << 32) - 65536
@@ -614,7 +609,7 @@ def atb2(pairs, tiles, wide=False):
     R = pairs[0][0].size(0)
     G = int(lib.dmp_atb2_blocks(bound, n))
     W = 2 * H if wide else H
-    jobs = (_Atb2Job * n)()
+    jobs = (_abi.dmp_atb2_job * n)()
     parts = []
     for j, (a, b) in enumerate(pairs):
         part = torch.empty((G, H * W), dtype=torch.float32, device=a.device)
@@ -741,25 +736,15 @@ def out_fwd_mfma(h1, W2, b2, gate, prev, W2t=None, dead_rows=0):
     return out
 
 
-_TYPED_JOB = None
-
-
 def typed_jobs(jobs, tiles):
     """Up to six products ``out = prev + prev2 + (a W + bias)`` (optionally through LeakyReLU) for the rows of ONE tile list in
     ONE launch (``dmp_out_fwd_typed``: grid.y = the job).  ``jobs``: dicts with ``a`` [R, H] (any row stride), ``W`` (``[in, out]``,
     or with ``w_in_out=False`` a Linear's ``[out, in]``; any row stride: a block of a wider matrix), ``out`` [R, H] view, and
     optionally ``bias``, ``prev``, ``prev2``, ``slope``.  Rows outside the tiles are not written."""
-    global _TYPED_JOB
-    import ctypes
     lib = _lib.load()
-    if _TYPED_JOB is None:
-        P, I64, I, F = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
-        _TYPED_JOB = type("dmp_typed_job", (ctypes.Structure,), {"_fields_": [
-            ("Hin", P), ("ldh", I64), ("W2", P), ("ldw", I64), ("w_in_out", I), ("bias", P), ("R", P), ("ldr", I64), ("R2", P), ("ldr2", I64),
-            ("act", I), ("slope", F), ("out", P), ("ldo", I64)]})
     slot_edge, tile_scale, num_tiles, bound = tiles
     R, H = jobs[0]["a"].shape
-    J = (_TYPED_JOB * len(jobs))()
+    J = (_abi.dmp_typed_job * len(jobs))()
     for j, q in zip(J, jobs):
         a, W, out = q["a"], q["W"], q["out"]
         prev, prev2, slope = q.get("prev"), q.get("prev2"), q.get("slope")
@@ -806,20 +791,14 @@ def out_fwd_typed_codes(h1, W2t, b2, enc, K, Wc, tiles, prev=None, out=None, w_i
     layer whose residual rows are the label embedding ``enc Wc`` -- added as one more 16-deep k-group of the product, so the [E, H] rows
     ``z0`` are neither written (``dmp_smallk_embed_live``) nor read.  ``row0``: the rows below it take no codes term (the pattern's
     edges, embedded by another table); ``prev`` may then hold just those rows ([row0 or more, H]: missing rows count as zeros)."""
-    global _TYPED_JOB
     lib = _lib.load()
-    if _TYPED_JOB is None:
-        P, I64, I, F = _ctypes.c_void_p, _ctypes.c_int64, _ctypes.c_int, _ctypes.c_float
-        _TYPED_JOB = type("dmp_typed_job", (_ctypes.Structure,), {"_fields_": [
-            ("Hin", P), ("ldh", I64), ("W2", P), ("ldw", I64), ("w_in_out", I), ("bias", P), ("R", P), ("ldr", I64), ("R2", P), ("ldr2", I64),
-            ("act", I), ("slope", F), ("out", P), ("ldo", I64)]})
     slot_edge, tile_scale, num_tiles, bound = tiles
     R, H = h1.shape
     if out is None:
         out = dead_rows_buffer((R, H), h1.device)
     Wc = Wc.detach()
     _lib.require_gpu(h1, W2t, out, prev, b2, enc, Wc)
-    j = _TYPED_JOB()
+    j = _abi.dmp_typed_job()
     j.Hin, j.ldh, j.W2, j.ldw, j.w_in_out = h1.data_ptr(), h1.stride(0), W2t.data_ptr(), W2t.stride(0), int(bool(w_in_out))
     j.bias = ptr(b2)
     j.R, j.ldr = ptr(prev), (prev.stride(0) if prev is not None else H)
@@ -1047,21 +1026,13 @@ def smallk_atb_cols(x, d, d2=None, out=None, H=None, mask=None, rows=None):
     return out
 
 
-_SMALLK_JOB = None
-
-
 def smallk_atb_jobs(jobs, H):
     """Several ``smallk_atb`` products of the same K and H in ONE launch (``dmp_smallk_atb_jobs``): ``jobs`` = up to four
     ``(x [R, K], d [R, H], out [K, H], mask or None)`` (``mask``: ``gate_row_mask`` words aligned to the job's first row).  The
     sums land in each job's ``out``."""
-    global _SMALLK_JOB
     lib = _lib.load()
-    if _SMALLK_JOB is None:
-        P, I64 = _ctypes.c_void_p, _ctypes.c_int64
-        _SMALLK_JOB = type("dmp_smallk_job", (_ctypes.Structure,), {"_fields_": [
-            ("X", P), ("ldx", I64), ("D", P), ("ldd", I64), ("gate", P), ("rowmask", P), ("R", I64), ("partial", P)]})
     K = jobs[0][0].size(1)
-    J = (_SMALLK_JOB * len(jobs))()
+    J = (_abi.dmp_smallk_job * len(jobs))()
     parts = []
     for n, (x, d, out, mask) in enumerate(jobs):
         R = x.size(0)
@@ -1102,20 +1073,11 @@ def l0_pack(enc_p, enc_g, gate=None, stacked=False):
     return out
 
 
-_L0_PACK_JOB = None
-
-
 def l0_pack_many(specs):
     """``[l0_pack(*spec) for spec in specs]`` (``spec`` = ``(enc_p, enc_g, gate, stacked)``; at most two) in ONE launch
     (``dmp_l0_pack_jobs``): a step's edge codes and node codes."""
-    global _L0_PACK_JOB
     lib = _lib.load()
-    if _L0_PACK_JOB is None:
-        P, I64, I = _ctypes.c_void_p, _ctypes.c_int64, _ctypes.c_int
-        _L0_PACK_JOB = type("dmp_l0_pack_job", (_ctypes.Structure,), {"_fields_": [
-            ("enc_p", P), ("ldp", I64), ("rows_p", I64), ("enc_g", P), ("ldg", I64), ("gate", P), ("rows_g", I64),
-            ("K", I), ("Kpad", I), ("goff", I), ("out", P)]})
-    J = (_L0_PACK_JOB * len(specs))()
+    J = (_abi.dmp_l0_pack_job * len(specs))()
     outs, keep = [], []
     for i, (enc_p, enc_g, gate, stacked) in enumerate(specs):
         _lib.require_gpu(enc_p, enc_g)
@@ -1188,15 +1150,6 @@ def _kept_row_tiles(mask, r0, r1):
 USE_GATE_BUNDLE = True      # the index arrays a step derives from its two 0 / 1 gates in three launches instead of ten (``gate_bundle``)
 
 
-class _RowMaskJob(_ctypes.Structure):
-    _fields_ = [("gate", _ctypes.c_void_p), ("R", _ctypes.c_int64), ("mask", _ctypes.c_void_p)]
-
-
-class _KeptJob(_ctypes.Structure):
-    _fields_ = [("mask", _ctypes.c_void_p), ("R", _ctypes.c_int64), ("tiles", _ctypes.c_int), ("scratch", _ctypes.c_void_p),
-                ("list", _ctypes.c_void_p), ("count", _ctypes.c_void_p)]
-
-
 def _mask_owner(gate):
     owner = gate._base if gate._base is not None else gate
     if owner.data_ptr() != gate.data_ptr() or owner.numel() != gate.numel():
@@ -1225,7 +1178,7 @@ def gate_bundle(index, v_gate, e_gate, want_nodes=False, l0_range=None, want_asc
         if hit is None or hit[0] != owner._version:
             todo.append((g, owner))
     if todo:
-        jobs = (_RowMaskJob * len(todo))()
+        jobs = (_abi.dmp_rowmask_job * len(todo))()
         masks = []
         for j, (g, owner) in enumerate(todo):
             R = g.numel()
@@ -1258,7 +1211,7 @@ def gate_bundle(index, v_gate, e_gate, want_nodes=False, l0_range=None, want_asc
     sel = want_nodes and E > 0 and (getattr(index, "_esel_nodes", None) is None or index._esel_nodes[0] is not vmask)
     if not lists and not sel:
         return
-    jobs = (_KeptJob * max(len(lists), 1))()
+    jobs = (_abi.dmp_kept_job * max(len(lists), 1))()
     keep = []
     for j, (m, R, tiles, memo, key) in enumerate(lists):
         cap = (R + 31) // 32 * 32 if tiles else R
@@ -1464,10 +1417,6 @@ class Layer0Codes:
                 if t[1][1] > t[1][0] or t[2][1] > t[2][0]]
 
 
-_ATB_JOB = None
-MAX_ATB_JOBS = 8
-
-
 def atb_rows_multi(products, tiles=None):
     """Several ``atb_rows`` products over the SAME rows in ONE launch: ``products`` = list of ``(a, b, gate, colsum[, mask])``
     (a [R, 128 ma], b [R, 128 nb]; ``mask``: a ``gate_row_mask`` whose zero bits mark rows where ``gate (.) a`` or ``b`` is
@@ -1476,14 +1425,7 @@ def atb_rows_multi(products, tiles=None):
     tile ranges per workgroup instead of paying every workgroup's fixed costs once per product.
     ``tiles`` (``NodeRows.tiles``): the products run over that tile list (rows gathered by slot: the kept nodes of a 0 / 1 node
     gate) instead of all rows -- jobs then carry neither gates, column sums nor masks: the list says which rows take part."""
-    global _ATB_JOB
-    import ctypes
     lib = _lib.load()
-    if _ATB_JOB is None:
-        P, I64, I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
-        _ATB_JOB = type("dmp_atb_job", (ctypes.Structure,), {"_fields_": [("A", P), ("lda", I64), ("B", P), ("ldb", I64), ("gate", P), ("partial", P),
-                                                                          ("partial_stride", I64), ("ldp", I), ("partial_colsum", P), ("cs_ld", I),
-                                                                          ("rowmask", P)]})
     R = products[0][0].size(0)
     products = [tuple(pr) + (None,) * (5 - len(pr)) for pr in products]
     if (tiles is not None and all(gate is None and not colsum and mask is None for _, _, gate, colsum, mask in products)
@@ -1496,7 +1438,7 @@ def atb_rows_multi(products, tiles=None):
         for i0 in range(0, len(blocks), 6):
             chunk = blocks[i0:i0 + 6]
             G = int(lib.dmp_atb2_blocks(bound, len(chunk)))
-            jobs2 = (_Atb2Job * len(chunk))()
+            jobs2 = (_abi.dmp_atb2_job * len(chunk))()
             parts2 = {}
             for j, (pi, ia, ib) in enumerate(chunk):
                 a, b = products[pi][0], products[pi][1]
@@ -1519,12 +1461,12 @@ def atb_rows_multi(products, tiles=None):
         return out
     blk = min(atb_block(a.size(1), b.size(1)) for a, b, _, _, _ in products)     # one block size per launch
     nblk = sum((a.size(1) // blk) * (b.size(1) // blk) for a, b, _, _, _ in products)
-    if nblk > MAX_ATB_JOBS:
-        raise ValueError("atb_rows_multi: more than %d output blocks" % MAX_ATB_JOBS)
+    if nblk > _abi.DMP_ATB_MAX_JOBS:
+        raise ValueError("atb_rows_multi: more than %d output blocks" % _abi.DMP_ATB_MAX_JOBS)
     if tiles is not None and any(gate is not None or colsum or mask is not None for _, _, gate, colsum, mask in products):
         raise _lib.DmpError("atb_rows_multi(tiles=...): jobs without gate, column sums or mask")
     G = int(lib.dmp_atb_tile_jobs_blocks(tiles[3], nblk, blk)) if tiles is not None else int(lib.dmp_atb_jobs_blocks_h(R, nblk, blk))
-    jobs = (_ATB_JOB * nblk)()
+    jobs = (_abi.dmp_atb_job * nblk)()
     parts, k = [], 0
     for a, b, gate, colsum, mask in products:
         M, N = a.size(1), b.size(1)
@@ -1588,17 +1530,6 @@ _FOLD_AUX_OUT = ("WesT", "nW2t", "eW2t")
 _FOLD_GRAD = ("nloop_w", "in_w", "out_w", "nbias", "eloop_w", "src_w", "dst_w", "ebias", "nW0", "eW0")
 
 
-def _struct(name, fields):
-    import ctypes
-    return type(name, (ctypes.Structure,), {"_fields_": [(f, ctypes.c_void_p) for f in fields]})
-
-
-_LayerWeights = _struct("dmp_layer_weights", _FOLD_IN + _FOLD_AUX_IN)
-_LayerFolded = _struct("dmp_layer_folded", _FOLD_OUT + _FOLD_AUX_OUT)
-_LayerFoldedGrads = _struct("dmp_layer_folded_grads", ["d" + f for f in _FOLD_OUT])
-_LayerWeightGrads = _struct("dmp_layer_weight_grads", _FOLD_GRAD)
-
-
 def _carve(buf, shapes):
     out, off = [], 0
     for shp in shapes:
@@ -1632,7 +1563,7 @@ class _FoldLayers(torch.autograd.Function):
         shapes = [(2 * H, H), (H,), (H, 3 * H), (H, 2 * H), (H,), (H, 2 * H), (H, H), (H, H)]
         per = sum(a[0] * (a[1] if len(a) > 1 else 1) for a in shapes)
         buf = torch.empty(L * per, dtype=torch.float32, device=dev)
-        W, F, outs, aux = (_LayerWeights * L)(), (_LayerFolded * L)(), [], []
+        W, F, outs, aux = (_abi.dmp_layer_weights * L)(), (_abi.dmp_layer_folded * L)(), [], []
         for l in range(L):
             pl = params[14 * l:14 * l + 14]
             for name, t in zip(_FOLD_IN + _FOLD_AUX_IN, pl + [eye]):
@@ -1658,7 +1589,7 @@ class _FoldLayers(torch.autograd.Function):
         shapes = [(H, H), (H, H), (H, H), (H,), (H, H), (H, H), (H, H), (H,), (H, H), (H, H)]
         per = 8 * H * H + 2 * H
         buf = torch.empty(L * per, dtype=torch.float32, device=params[0].device)
-        G, D, out, keep = (_LayerFoldedGrads * L)(), (_LayerWeightGrads * L)(), [None], []
+        G, D, out, keep = (_abi.dmp_layer_folded_grads * L)(), (_abi.dmp_layer_weight_grads * L)(), [None], []
         fshapes = [(2 * H, H), (H,), (H, 3 * H), (H, 2 * H), (H,)]
         for l in range(L):
             gl = []
@@ -1709,7 +1640,6 @@ def fold_layers(layers):
     return out
 
 
-_GEMM_TYPES = None
 SMALL_GEMM_MAX_ROWS = 1024     # output rows up to which a product goes into the small-product launch (latency-oriented: a column per thread)
 
 
@@ -1717,24 +1647,11 @@ def small_gemm_jobs(jobs):
     """Several small fp32 products in ONE launch (``dmp_small_gemm_jobs``, csrc/dmp_fold.hip).  ``jobs``: list of
     ``(out, terms, addend)`` with ``terms`` a list of ``(A, transA, B, transB)`` -- ``out = sum_t op(A_t) op(B_t) (+ addend)``,
     ``op(X) = X^T`` when the flag is set; operands are 2-D fp32 tensors with unit inner stride (any row stride: column slices
-    and ``out`` views of wider tensors are fine), ``out`` must not alias an operand.  At most 12 jobs of at most 3 terms."""
-    global _GEMM_TYPES
-    import ctypes
+    and ``out`` views of wider tensors are fine), ``out`` must not alias an operand.  At most ``DMP_GEMM_MAX_JOBS`` jobs of at most ``DMP_GEMM_MAX_TERMS`` terms."""
     lib = _lib.load()
-    if _GEMM_TYPES is None:
-        class _Term(ctypes.Structure):
-            _fields_ = [("A", ctypes.c_void_p), ("lda", ctypes.c_int64), ("B", ctypes.c_void_p), ("ldb", ctypes.c_int64),
-                        ("transA", ctypes.c_int32), ("transB", ctypes.c_int32), ("K", ctypes.c_int32), ("pad", ctypes.c_int32)]
-
-        class _Job(ctypes.Structure):
-            _fields_ = [("term", _Term * 3), ("C0", ctypes.c_void_p), ("ldc0", ctypes.c_int64), ("C", ctypes.c_void_p),
-                        ("ldc", ctypes.c_int64), ("num_terms", ctypes.c_int32), ("M", ctypes.c_int32), ("N", ctypes.c_int32),
-                        ("pad", ctypes.c_int32)]
-        _GEMM_TYPES = (_Term, _Job)
-    _, Job = _GEMM_TYPES
-    if not 0 < len(jobs) <= 12:
-        raise _lib.DmpError("small_gemm_jobs: 1..12 jobs")
-    J = (Job * len(jobs))()
+    if not 0 < len(jobs) <= _abi.DMP_GEMM_MAX_JOBS:
+        raise _lib.DmpError("small_gemm_jobs: 1..%d jobs" % _abi.DMP_GEMM_MAX_JOBS)
+    J = (_abi.dmp_gemm_job * len(jobs))()
 
     def ld(t):
         if t.dim() != 2 or t.dtype != torch.float32 or (t.size(1) > 1 and t.stride(1) != 1):
@@ -1744,8 +1661,8 @@ def small_gemm_jobs(jobs):
     keep = []
     for n, (out, terms, addend) in enumerate(jobs):
         M, N = out.shape
-        if not 0 < len(terms) <= 3:
-            raise _lib.DmpError("small_gemm_jobs: 1..3 terms per job")
+        if not 0 < len(terms) <= _abi.DMP_GEMM_MAX_TERMS:
+            raise _lib.DmpError("small_gemm_jobs: 1..%d terms per job" % _abi.DMP_GEMM_MAX_TERMS)
         _lib.require_gpu(out, addend, *[x for tm in terms for x in (tm[0], tm[2])])
         for q, (A, ta, B, tb) in enumerate(terms):
             K = A.size(0) if ta else A.size(1)

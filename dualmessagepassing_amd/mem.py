@@ -18,7 +18,9 @@ are zero with mask 0.  n' > M: stride = n' // M, k = n' - (M - 1) stride, slot i
 """
 import torch as th
 
-MODES = {"mean": 0, "sum": 1, "max": 2}
+from . import _abi
+
+MODES = {"mean": _abi.DMP_MEM_MEAN, "sum": _abi.DMP_MEM_SUM, "max": _abi.DMP_MEM_MAX}
 UNBUILT = ("attn", "lstm", "circular_attn", "circular_lstm")
 
 

@@ -13,7 +13,7 @@ Math (reference SubgraphCountingMatching/models/dmpnn.py:1
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _abi, _lib
 from ._lib import check, ptr, stream_ptr
 
 
@@ -808,23 +808,6 @@ class PoolIndex:
         self.flag8 = None if flag is None else flag.view(-1).to(torch.uint8).contiguous()
 
 
-_POOL_JOB = None
-
-
-def _pool_job_type():
-    global _POOL_JOB
-    if _POOL_JOB is None:
-        import ctypes
-        P, I = ctypes.c_void_p, ctypes.c_int64
-
-        class _Job(ctypes.Structure):
-            _fields_ = [("sizes_a", P), ("sizes_b", P), ("Ba", I), ("Bb", I), ("flag_a", P), ("flag_b", P), ("rows_a", I), ("R", I),
-                        ("chunk", ctypes.c_int), ("off", P), ("gptr", P), ("vptr", P), ("vent", P), ("gent", P), ("seg", P),
-                        ("flag8", P), ("rowmap", P), ("sizes", P)]
-        _POOL_JOB = _Job
-    return _POOL_JOB
-
-
 def _pool_prepare(self, pieces, flag, seg, R, job):
     """Allocate this index's arrays and describe its build as one ``dmp_pool_job``."""
     sizes = [p.view(-1).to(torch.int64).contiguous() for p in pieces]
@@ -867,7 +850,7 @@ def _pool_prepare(self, pieces, flag, seg, R, job):
 
 
 def _pool_build_device(self, pieces, flag, seg, R):
-    J = (_pool_job_type() * 1)()
+    J = (_abi.dmp_pool_job * 1)()
     _pool_prepare(self, pieces, flag, seg, R, J[0])
     check(_lib.load().dmp_pool_index_jobs(J, 1, stream_ptr()), "dmp_pool_index_jobs")
 
@@ -877,9 +860,9 @@ def pool_indexes(specs):
     ``(sizes, flag, num_rows)`` as ``PoolIndex(sizes, flag, num_rows=...)`` takes them (device tensors)."""
     out = [PoolIndex.__new__(PoolIndex) for _ in specs]
     lib = _lib.load()
-    for i in range(0, len(specs), 4):                    # DMP_POOL_MAX_JOBS
-        part = specs[i:i + 4]
-        J = (_pool_job_type() * len(part))()
+    for i in range(0, len(specs), _abi.DMP_POOL_MAX_JOBS):
+        part = specs[i:i + _abi.DMP_POOL_MAX_JOBS]
+        J = (_abi.dmp_pool_job * len(part))()
         for k, (sizes, flag, rows) in enumerate(part):
             pieces = sizes if isinstance(sizes, (tuple, list)) else (sizes,)
             _pool_prepare(out[i + k], pieces, flag, None, int(rows), J[k])

@@ -60,29 +60,6 @@ class _PooledHead(th.autograd.Function):
         return dps, dgs, None, None, None, None, dWp, dbp, dWg, dbg, dW1, db1, dW2, db2, None
 
 
-_HEAD_STRUCTS = None
-
-
-def _head_structs():
-    """ctypes mirrors of dmp_head_weights / dmp_head_io / dmp_head_grads (include/dmp_hip.h), built once."""
-    global _HEAD_STRUCTS
-    if _HEAD_STRUCTS is None:
-        _HEAD_STRUCTS = _make_head_structs()
-    return _HEAD_STRUCTS
-
-
-def _make_head_structs():
-    import ctypes
-    P, I64, F32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_float
-    W = type("dmp_head_weights", (ctypes.Structure,), {"_fields_": [(n, P) for n in ("Wp", "bp", "Wg", "bg", "W1", "b1", "W2", "b2")]})
-    IO = type("dmp_head_io", (ctypes.Structure,), {"_fields_": [("ps", P), ("ld_ps", I64), ("gs", P), ("ld_gs", I64), ("pl", P), ("gl", P),
-                                                                ("scale_p", F32), ("scale_g", F32), ("F", P), ("Y1S", P), ("y", P)]})
-    G = type("dmp_head_grads", (ctypes.Structure,), {"_fields_": [("dy", P), ("dy_scale", P), ("dY1", P), ("dP", P), ("dG", P), ("dps", P),
-                                                                  ("ld_dps", I64), ("dgs", P), ("ld_dgs", I64)]
-                                                     + [(n, P) for n in ("dWp", "dbp", "dWg", "dbg", "dW1", "db1", "dW2", "db2")]})
-    return W, IO, G
-
-
 class _PooledHeadsHIP(th.autograd.Function):
     """All pooled heads of the model and their blend in three HIP launches (csrc/dmp_heads.hip):
     ``pred = sum_i blend_i * head_i(sums_i[:B], sums_i[B:])``.  Inputs per head: ``sums`` [2B, H] (pattern rows, then
@@ -91,14 +68,13 @@ class _PooledHeadsHIP(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, n_heads, slope, *args):
-        from . import _lib
+        from . import _abi, _lib
         lib = _lib.load()
-        Wt, IOt, Gt = _head_structs()
         per = 6 + 8
         heads = [args[i * per:(i + 1) * per] for i in range(n_heads)]
         B = heads[0][0].size(0) // 2
         dev = heads[0][0].device
-        W, IO = (Wt * n_heads)(), (IOt * n_heads)()
+        W, IO = (_abi.dmp_head_weights * n_heads)(), (_abi.dmp_head_io * n_heads)()
         keep, ys = [], []
         for i, (sums, pl, gl, sp, sg, blend, Wp, bp, Wg, bg, W1, b1, W2, b2) in enumerate(heads):
             if sums.stride(1) != 1 or sums.stride(0) % 4 or sums.data_ptr() % 16:   # the kernels take any 16-byte-aligned row stride
@@ -139,13 +115,12 @@ class _PooledHeadsHIP(th.autograd.Function):
 
     @staticmethod
     def backward(ctx, d):
-        from . import _lib
+        from . import _abi, _lib
         lib = _lib.load()
-        _, _, Gt = _head_structs()
         W, IO = ctx.structs
         n, B = ctx.n, ctx.B
         d = d.contiguous().float()
-        G = (Gt * n)()
+        G = (_abi.dmp_head_grads * n)()
         grads, hold = [None, None], []
         for i, (sums, pl_, gl_, F, Y1S, blend, prm) in enumerate(ctx.keep):
             h = prm[0].size(0)
