@@ -693,11 +693,15 @@ def apply_mlp(seq, x, rows_dev=None):
 
 def masked_batch_norm(bn, x, rows_dev):
     """Training-mode ``BatchNorm1d`` over the first ``rows_dev[0]`` rows of ``x`` with tensor ops (no host sync: it records):
-    statistics and running averages from those rows only, zeros in the others -- what ``batch_norm_act(rows_dev=...)`` does
-    for the widths the HIP kernels take."""
+    statistics from those rows only, zeros in the others -- what ``batch_norm_act(rows_dev=...)`` does for the widths the HIP
+    kernels take, including its clamp of the count to ``[1, rows of x]`` and its one-row case (variance 0, which the module
+    refuses).  The module's side effects are the module's: ``num_batches_tracked`` counts the call, and the running averages
+    move by ``momentum``, or by the cumulative average ``1 / num_batches_tracked`` when ``momentum`` is None, towards the batch
+    mean and the unbiased batch variance (the biased one for a single row)."""
     R = x.size(0)
-    n = rows_dev.to(x.dtype).clamp(min=1.0)
-    m = (torch.arange(R, device=x.device) < rows_dev).to(x.dtype).unsqueeze(1)
+    count = rows_dev.clamp(min=1, max=R)
+    n = count.to(x.dtype)
+    m = (torch.arange(R, device=x.device) < count).to(x.dtype).unsqueeze(1)
     mean = (x * m).sum(0) / n
     d = (x - mean) * m
     var = (d * d).sum(0) / n
@@ -706,8 +710,8 @@ def masked_batch_norm(bn, x, rows_dev):
         y = y * bn.weight + bn.bias
     with torch.no_grad():
         if bn.track_running_stats and bn.running_mean is not None:
-            mom = bn.momentum if bn.momentum is not None else 0.1
             bn.num_batches_tracked.add_(1)
+            mom = bn.momentum if bn.momentum is not None else 1.0 / bn.num_batches_tracked.to(x.dtype)
             bn.running_mean.mul_(1 - mom).add_(mom * mean.detach())
             bn.running_var.mul_(1 - mom).add_(mom * (var.detach() * n / (n - 1.0).clamp(min=1.0)))
     return y * m

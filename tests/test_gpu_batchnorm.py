@@ -86,9 +86,7 @@ def test_batch_norm_over_the_real_rows_of_a_padded_batch(cap, rows, c, slope, gp
     act = (lambda t: t) if slope is None else th.nn.LeakyReLU(slope)
     xa, xb = x0.clone().requires_grad_(True), x0[:rows].clone().requires_grad_(True)
     ya = ops.batch_norm_act(bn_a, xa, slope, n_dev)
-    yb = act(bn_b(xb)) if rows > 1 else None
-    if yb is None:                                               # torch refuses one row; fp64 by hand (variance 0)
-        return
+    yb = act(bn_b(xb))                                           # (one live row, which torch refuses: test_gpu_bn_fp64.py)
     ga = th.autograd.grad(ya, [xa, bn_a.weight, bn_a.bias], dy)
     gb = th.autograd.grad(yb, [xb, bn_b.weight, bn_b.bias], dy[:rows])
     assert float(ya[rows:].abs().max()) == 0.0 if rows < cap else True

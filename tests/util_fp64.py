@@ -1,5 +1,6 @@
-"""Float64 CPU restatements of the CNN layer, the RNN layer and the relational conv, written from the operators' public
-definitions (not by running the code under test in double), and the case lists that ``test_fp64_refs_cpu.py`` and the three
+"""Float64 CPU restatements of the CNN layer, the RNN layer, the relational conv, the pooled prediction heads and their blend,
+the count loss and training-mode BatchNorm (+ activation) over the live rows of a padded batch, written from the operators'
+public definitions (not by running the code under test in double), and the case lists that ``test_fp64_refs_cpu.py`` and the
 ``test_gpu_*_fp64.py`` modules share, so the CPU check of the yardsticks covers exactly what the GPU modules run.
 
 Distances are measured as everywhere in the suite: ``max |a - ref| <= tol * max(1, max |ref|)``."""
@@ -94,20 +95,31 @@ def cnn_layer_fp64(weight, bias, x, gate, k, pad, pk, pp, slope, residual, act=T
     return y, g, safe.transpose(1, 2), arg.transpose(1, 2)
 
 
-def batch_norm_fp64(p, weight, bias, mean, var, training, momentum, eps, tracked):
+def batch_norm_fp64(p, weight, bias, mean, var, training, momentum, eps, tracked, n=None, slope=None):
     """nn.BatchNorm1d over all rows of p [B, L', H]: (out, running mean, running var after the call).  ``momentum`` None is
-    the cumulative average 1 / (batches tracked, this one included)."""
-    rows = p.reshape(-1, p.size(-1))
+    the cumulative average 1 / (batches tracked, this one included).  ``weight`` / ``bias`` None: not affine.  Training mode
+    only: ``n`` (1 <= n <= rows): only the first n rows exist -- the statistics are theirs, the other rows of the output (and
+    so of dx) are zeros; one row has variance 0 and leaves ``running_var`` the biased value.  ``slope``: the negative slope of
+    an activation after the normalisation (None: none, 0: relu)."""
+    gam = 1.0 if weight is None else weight
+    bet = 0.0 if bias is None else bias
     if not training:
-        return (p - mean) / th.sqrt(var + eps) * weight + bias, mean, var
-    n = rows.size(0)
-    m = rows.mean(0)
-    v = ((rows - m) ** 2).mean(0)
+        return (p - mean) / th.sqrt(var + eps) * gam + bet, mean, var
+    rows = p.reshape(-1, p.size(-1))
+    n = rows.size(0) if n is None else n
+    live = rows[:n]
+    m = live.mean(0)
+    v = ((live - m) ** 2).mean(0)
     f = 1.0 / (tracked + 1) if momentum is None else momentum
     with th.no_grad():
         new_mean = (1 - f) * mean + f * m
         new_var = (1 - f) * var + f * v * n / max(n - 1, 1)
-    return (p - m) / th.sqrt(v + eps) * weight + bias, new_mean, new_var
+    out = (live - m) / th.sqrt(v + eps) * gam + bet
+    if slope is not None:
+        out = th.where(out > 0, out, out * slope)
+    if n < rows.size(0):
+        out = th.cat([out, out.new_zeros(rows.size(0) - n, rows.size(1))])
+    return out.reshape(p.shape), new_mean, new_var
 
 
 def cnn_geometries():
@@ -439,3 +451,282 @@ def relconv_make(c, seed=0):
 
 def stable_seed(name):
     return sum((i + 1) * ord(ch) for i, ch in enumerate(name)) % 100003
+
+
+# ---------------------------------------------------------------------------------------------------------- pooled heads
+
+HEADS_TIE = 1e-5            # a row is unsafe when a pre-activation of its hidden layer lies within this share of max |pre| of zero
+HEADS_UNSAFE_ROWS = 0.02    # at most this share of the rows of a case with B >= 255 (none at B <= 17: the seed is chosen so)
+FP32_SHARE = 0.25           # the fp32 tensor-op restatement stays within this share of a non-band case's tolerance (asserted)
+HEAD_PARAMS = ("Wp", "bp", "Wg", "bg", "W1", "b1", "W2", "b2")
+HEADS_MAX = 2               # DMP_HEADS_MAX of include/dmp_hip.h (tests/test_lib_abi.py holds the binding to the header)
+
+
+def leaky(v, slope):
+    """torch's leaky_relu: the negative slope at v <= 0 (slope 0: relu)."""
+    return th.where(v > 0, v, v * slope)
+
+
+def heads_fp64(params, ps, gs, pl, gl, scale_p, scale_g, slope):
+    """The pooled count head: p = ps Wp^T + scale_p bp, g = gs Wg^T + scale_g bg, s = [pl, gl, 1/pl, 1/gl],
+    f = [p | g | g - p | g * p | s], y1 = act(f W1^T + b1), y = [y1 | s] W2^T + b2.  ``params``: Wp, bp, Wg, bg, W1, b1, W2, b2
+    in nn.Linear layout; ps, gs [B, H]; pl, gl [B, 1].  Returns (y [B, 1], the pre-activation [B, H], safe [B] bool: no entry of
+    the row's pre-activation within HEADS_TIE max |pre| of zero).  Runs in the dtype of its arguments."""
+    Wp, bp, Wg, bg, W1, b1, W2, b2 = params
+    p = ps @ Wp.t() + scale_p * bp
+    g = gs @ Wg.t() + scale_g * bg
+    s = th.cat([pl, gl, 1.0 / pl, 1.0 / gl], 1)
+    f = th.cat([p, g, g - p, g * p, s], 1)
+    pre = f @ W1.t() + b1
+    y = th.cat([leaky(pre, slope), s], 1) @ W2.t() + b2
+    with th.no_grad():
+        safe = (pre.abs() > HEADS_TIE * pre.abs().max()).all(1)
+    return y, pre.detach(), safe
+
+
+def heads_blend_fp64(ys, gls):
+    """Blend by the sizes of the target graphs: weights gl_i / sum_j gl_j (list of [B, 1]), the blended count sum_i w_i y_i."""
+    total = sum(gls)
+    ws = [g / total for g in gls]
+    return sum(w * y for w, y in zip(ws, ys)), ws
+
+
+def heads_cases():
+    """ids -> dict(H, slope, B, heads, blend (None, "given", "len"), pool ("sum": bias factors L; "mean": 1), stride (None, "pass":
+    a column slice the op passes through, "copy": one it has to copy), lmax (pl, gl in 1..8 / 1..64, or both in 1..lmax), band).
+
+    Every B at both widths with every slope; the head count and the blend, the bias factors and the row stride rotate over the
+    six cases of a B, shifted from one B to the next, so each meets every tile edge; ``band``: B >= 1024."""
+    cases = {}
+    combos = [(1, None), (2, "given"), (2, "len"), (2, None)]
+    strides = [None, "pass", "copy"]
+    for hi, H in enumerate((64, 128)):
+        for bi, B in enumerate((1, 3, 15, 16, 17, 255, 256, 257, 1024, 1025)):
+            for si, slope in enumerate((0.0, 1.0 / 5.5, 0.01)):
+                k = 3 * hi + si                                   # 0 .. 5 within one B: all four combos, all three strides
+                heads, blend = combos[(k + bi) % 4]
+                pool, stride = "mean" if (k + bi) % 3 == 0 else "sum", strides[(k + 2 * bi) % 3]
+                cases["H%d-B%d-s%.2g-%dh-%s-%s-%s" % (H, B, slope, heads, blend or "sum", pool, stride or "dense")] = dict(
+                    H=H, slope=slope, B=B, heads=heads, blend=blend, pool=pool, stride=stride, lmax=None, band=B >= 1024)
+    cases["H128-B257-len512"] = dict(H=128, slope=1.0 / 5.5, B=257, heads=2, blend="len", pool="sum", stride=None, lmax=512, band=False)
+    cases["H64-B17-len512"] = dict(H=64, slope=0.0, B=17, heads=1, blend=None, pool="sum", stride="pass", lmax=512, band=False)
+    return cases
+
+
+def heads_stride_geometry(H, kind):
+    """(width of the matrix the rows are a column slice of, first column).  "pass": stride H + 8 and a start 16 bytes in, which
+    the kernels take as they are; "copy": stride H + 6, no multiple of 4."""
+    return {None: (H, 0), "pass": (H + 8, 4), "copy": (H + 6, 1)}[kind]
+
+
+def heads_inputs(name):
+    """The CPU inputs of a case: dict(params: per head the eight tensors N(0, 0.2); wide: per head [2B, width] N(0, 1), of which
+    columns c0 .. c0 + H are the pattern sums (rows < B) and the target sums; pl, gl: per head [B, 1]; Lp, Lg: the padded
+    lengths; scale_p, scale_g; blends: per head [B, 1] or None; cot [B, 1]; c0).  At B <= 17 the first seed at which no row of
+    any head is unsafe."""
+    c = heads_cases()[name]
+    H, B, n = c["H"], c["B"], c["heads"]
+    width, c0 = heads_stride_geometry(H, c["stride"])
+    Lp, Lg = (8.0, 64.0) if c["lmax"] is None else (float(c["lmax"]),) * 2
+    sp, sg = (Lp, Lg) if c["pool"] == "sum" else (1.0, 1.0)
+    for seed in range(stable_seed(name), stable_seed(name) + 64):
+        g = th.Generator().manual_seed(seed)
+        params = [[th.randn(shape, generator=g) * 0.2 for shape in ((H, H), (H,), (H, H), (H,), (H, 4 * H + 4), (H,), (1, H + 4), (1,))]
+                  for _ in range(n)]
+        wide = [th.randn(2 * B, width, generator=g) for _ in range(n)]
+        pls = [th.randint(1, int(Lp) + 1, (B, 1), generator=g).float() for _ in range(n)]
+        gls = [th.randint(1, int(Lg) + 1, (B, 1), generator=g).float() for _ in range(n)]
+        cot = th.randn(B, 1, generator=g)
+        blends = [None] * n
+        if c["blend"] == "given":
+            blends = [gl / sum(gls) for gl in gls]
+        d = dict(params=params, wide=wide, pl=pls, gl=gls, Lp=Lp, Lg=Lg, scale_p=sp, scale_g=sg, blends=blends, cot=cot, c0=c0)
+        if B > 17 or bool(heads_reference(c, d)["safe"].all()):
+            return d
+    raise AssertionError("no seed without an unsafe row for " + name)
+
+
+def heads_reference(c, d, dtype=th.float64, device="cpu", safe=None):
+    """The blended count of a case and, with the cotangent zeroed on the unsafe rows, d wide and the eight parameter gradients
+    per head, from ``heads_fp64`` / ``heads_blend_fp64`` in ``dtype`` (float64: the reference; float32: the tensor-op
+    yardstick, which takes the reference's ``safe``)."""
+    H, B, c0 = c["H"], c["B"], d["c0"]
+    cast = lambda t: t.detach().to(device=device, dtype=dtype)
+    params = [[cast(t).requires_grad_(True) for t in head] for head in d["params"]]
+    wide = [cast(t).requires_grad_(True) for t in d["wide"]]
+    ys, ok = [], th.ones(B, dtype=th.bool, device=device)
+    for prm, w, pl, gl in zip(params, wide, d["pl"], d["gl"]):
+        y, _, s = heads_fp64(prm, w[:B, c0:c0 + H], w[B:, c0:c0 + H], cast(pl), cast(gl), d["scale_p"], d["scale_g"], c["slope"])
+        ys.append(y)
+        ok &= s
+    if c["blend"] == "len":
+        y = heads_blend_fp64(ys, [cast(g) for g in d["gl"]])[0]
+    else:
+        y = sum(yi if b is None else cast(b) * yi for yi, b in zip(ys, d["blends"]))
+    safe = ok if safe is None else safe.to(device)
+    (y * cast(d["cot"]) * safe.view(-1, 1).to(dtype)).sum().backward()
+    return dict(y=y.detach(), safe=safe.cpu(), dwide=[w.grad for w in wide], dparams=[[t.grad for t in head] for head in params])
+
+
+# ------------------------------------------------------------------------------------------------------------ count loss
+
+LOSS_KINDS = ("MSE", "MAE", "SMSE")          # kind 0, 1, 2 of dmp_count_loss; SMSE: smooth L1 with beta 1
+
+
+def count_loss_fp64(pred, target, kind, slope):
+    """mean_i crit(act(pred_i) - target_i) and its gradient by pred, in double: act = leaky_relu(slope) with the negative slope
+    at pred <= 0; MSE d^2; MAE |d| with sign(0) = 0; smooth L1 d^2 / 2 inside |d| < 1 and |d| - 1/2 from |d| = 1 on."""
+    p, t = pred.detach().cpu().double().reshape(-1), target.detach().cpu().double().reshape(-1)
+    da = th.where(p > 0, th.ones_like(p), th.full_like(p, slope))
+    d = p * da - t
+    if kind == "MSE":
+        v, g = d * d, 2 * d
+    elif kind == "MAE":
+        v, g = d.abs(), th.sign(d)
+    else:
+        inside = d.abs() < 1
+        v, g = th.where(inside, 0.5 * d * d, d.abs() - 0.5), th.where(inside, d, th.sign(d))
+    return v.mean(), (g * da / p.numel()).reshape(pred.shape)
+
+
+def count_loss_cases():
+    """ids -> (n, kind, slope, band): n on both sides of the workgroup's 1024 threads, the three criteria, slopes 1 (no
+    activation), 0.01 and 0 (relu); ``band``: n = 65537."""
+    return {"n%d-%s-s%g" % (n, kind, slope): (n, kind, slope, n == 65537)
+            for n in (1, 2, 1023, 1024, 1025, 4096, 65537) for kind in LOSS_KINDS for slope in (1.0, 0.01, 0.0)}
+
+
+def count_loss_inputs(name):
+    """(pred [n, 1] N(0, 3), target [n, 1] integers 0 .. 5).  The first min(n, 16) entries sit exactly on the kinks, four kinds in
+    turn starting at one the case's name picks (so n = 1 and n = 2 meet all of them over the cases): pred = 0;
+    act(pred) = target; act(pred) - target = 1; act(pred) - target = -1.  All of these are exact in fp32."""
+    n, kind, slope, _ = count_loss_cases()[name]
+    g = th.Generator().manual_seed(stable_seed(name))
+    pred = th.randn(n, 1, generator=g) * 3
+    target = th.randint(0, 6, (n, 1), generator=g).float()
+    for i in range(min(n, 16)):
+        t = float(target[i])
+        k = (i + stable_seed(name)) % 4
+        if k == 0:
+            pred[i] = 0.0
+        elif k == 1:
+            pred[i] = t                                   # t = 0: pred = 0 is on two kinks at once
+        elif k == 2:
+            pred[i] = t + 1.0
+        elif t >= 2:
+            pred[i] = t - 1.0
+        else:
+            pred[i], target[i] = 0.0, 1.0                 # act(0) = 0 whatever the slope
+    return pred, target
+
+
+# -------------------------------------------------------------------------------------------------------------- BatchNorm
+
+BN_WIDTHS = (4, 8, 16, 32, 64, 128, 256, 512, 1024)      # every width csrc/dmp_bn.hip admits: C / 4 divides 256, C <= 1024
+BN_SLOPES = (None, 0.0, 1.0 / 5.5)
+BN_VAR_FLOOR = 1.0          # of a column over two or three live rows (see bn_inputs); the rows are drawn with variance 9
+
+
+def bn_rows(C):
+    """Row counts around the rows a workgroup takes per pass (256 lanes, C / 4 lanes per row)."""
+    rpp = 256 // (C // 4)
+    return sorted({2, 3, rpp - 1, rpp, rpp + 1, 4 * rpp + 1} - {0, 1})
+
+
+def bn_cases():
+    """ids -> dict(C, affine, runs: [(R, live row count or None, slope)], outlier, band, momentum).
+
+    "C<width>-affine<0/1>": every row count of ``bn_rows`` with every slope.  "long-*": 70001 x 128 (band) and 10858 x 256.
+    "pad-C*": a batch padded to cap = 4 rows_per_pass + 3 rows (259 for "pad-C16-plain": not affine, no activation) with live counts 1, 2, cap - 1, cap, and 0 and cap + 7, which the
+    kernel clamps to 1 and cap.  "outlier-*" (band): row 0 at 50 standard deviations from the column mean."""
+    cases = {}
+    for C in BN_WIDTHS:
+        for affine in (True, False):
+            cases["C%d-affine%d" % (C, affine)] = dict(C=C, affine=affine, runs=[(R, None, s) for R in bn_rows(C) for s in BN_SLOPES],
+                                                       outlier=False, band=False, momentum=0.1 if affine else 0.3)
+    cases["long-128"] = dict(C=128, affine=True, runs=[(70001, None, 1.0 / 5.5)], outlier=False, band=True, momentum=0.1)
+    cases["long-256"] = dict(C=256, affine=True, runs=[(10858, None, 0.0)], outlier=False, band=False, momentum=0.1)
+    for i, C in enumerate((8, 64, 256, 1024)):
+        cap = 4 * (256 // (C // 4)) + 3
+        cases["pad-C%d" % C] = dict(C=C, affine=True, outlier=False, band=False, momentum=0.1,
+                                    runs=[(cap, n, BN_SLOPES[(i + j) % 3]) for j, n in enumerate((1, 2, cap - 1, cap, 0, cap + 7))])
+    # not affine: one live row comes out as exact zeros, which an activation would have to be masked on entirely
+    cases["pad-C16-plain"] = dict(C=16, affine=False, outlier=False, band=False, momentum=0.3,
+                                  runs=[(259, n, None) for n in (1, 2, 258, 259, 0, 266)])
+    cases["outlier-256"] = dict(C=256, affine=True, runs=[(2708, None, 1.0 / 5.5)], outlier=True, band=True, momentum=0.1)
+    cases["outlier-128"] = dict(C=128, affine=True, runs=[(70001, None, None)], outlier=True, band=True, momentum=0.1)
+    return cases
+
+
+def bn_live(R, n):
+    """The row count the kernels use for a device-side count n on a batch of capacity R: clamped to [1, R]."""
+    return R if n is None else min(max(n, 1), R)
+
+
+def bn_inputs(name, run, C=None):
+    """(x [R, C], dy [R, C], gamma, beta, running mean, running var) of run ``run`` of a case: rows 3 N(0, 1) + 5 N(0, 1) per
+    column (means far from 0), as ``test_gpu_batchnorm.py`` draws them; +-1e6 in the padding rows of x and dy; with ``outlier``
+    row 0 sits 50 standard deviations of the other rows above their mean; with two or three live rows no column's variance is
+    under BN_VAR_FLOOR."""
+    c = bn_cases()[name]
+    C = C or c["C"]
+    R, n, _ = c["runs"][run]
+    g = th.Generator().manual_seed(stable_seed(name) + run)
+    x = th.randn(R, C, generator=g) * 3.0 + th.randn(C, generator=g) * 5.0
+    dy = th.randn(R, C, generator=g)
+    gamma, beta = th.rand(C, generator=g) + 0.5, th.randn(C, generator=g)
+    mean, var = th.randn(C, generator=g), th.rand(C, generator=g) + 0.5
+    if c["outlier"]:
+        x[0] = x[1:].mean(0) + 50.0 * x[1:].std(0)
+    live = bn_live(R, n)
+    bn_floor_rows(x, live)
+    if n is not None:
+        x[live:] = 1e6
+        dy[live:] = -1e6
+        x[live::2] = -1e6
+    return x, dy, gamma, beta, mean, var
+
+
+def bn_floor_rows(x, live):
+    if 2 <= live <= 3:
+        # two or three rows that nearly agree in a column: half an ulp of the column mean (|x| up to 30: 1e-6) moves xhat by
+        # 1e-6 / sqrt(var + eps), up to 3e-4, in any fp32 statement, the tensor ops' included, and dx, which all but cancels
+        # over two rows, by as much.  A column under the floor gets its second row put four above its first (the rows are
+        # drawn with standard deviation 3).
+        flat = x[:live].double().var(0, unbiased=False) < BN_VAR_FLOOR
+        x[1, flat] = x[0, flat] + 4.0
+
+
+def bn_reference(x, dy, gamma, beta, mean, var, momentum, eps, live, slope, steps=2, dtype=th.float64, safe=None, tracked=0):
+    """``steps`` consecutive training calls of BatchNorm (+ activation) on the same rows through ``batch_norm_fp64`` in
+    ``dtype``: dict(y, mean, var (the running statistics after the last call), dx, dgamma, dbeta (of the last call, the
+    upstream gradient zeroed where ``safe`` is False), safe: |the value before the activation| > TAU, all True without one)."""
+    cast = lambda t: None if t is None else t.detach().cpu().to(dtype)
+    xd = cast(x).requires_grad_(True)
+    gd, bd = (None, None) if gamma is None else (cast(gamma).requires_grad_(True), cast(beta).requires_grad_(True))
+    m, v = cast(mean), cast(var)
+    for step in range(steps):
+        pre, _, _ = batch_norm_fp64(xd, gd, bd, m, v, True, momentum, eps, tracked + step, n=live)
+        y, m, v = batch_norm_fp64(xd, gd, bd, m, v, True, momentum, eps, tracked + step, n=live, slope=slope)
+    if safe is None:
+        safe = th.ones_like(pre, dtype=th.bool) if slope is None else pre.detach().abs() > TAU
+        safe[live:] = True                                # padding rows: the output and dx are zeros whatever arrives
+    grads = th.autograd.grad(y, [xd] + ([] if gd is None else [gd, bd]), th.where(safe, cast(dy), th.zeros((), dtype=dtype)))
+    return dict(y=y.detach(), mean=m, var=v, dx=grads[0], dgamma=None if gd is None else grads[1],
+                dbeta=None if gd is None else grads[2], safe=safe)
+
+
+MASKED_BN_RUNS = [(1024, n, momentum) for n in (1, 3, 700, 0, 1031) for momentum in (0.1, None)]   # (cap, rows_dev, momentum)
+
+
+def masked_bn_inputs(cap, n, C=64):
+    """(x [cap, C], dy, gamma, beta, running mean, running var) for ``ops.masked_batch_norm``: 64 columns, of which the first 50
+    are the reference's shipped UNC width (no multiple of 4: tensor ops) and all 64 the next width the kernels take (52 is
+    none: 13 lanes per row do not divide a workgroup's 256); +-1e4 in the padding rows."""
+    g = th.Generator().manual_seed(cap + n + C)
+    x = th.randn(cap, C, generator=g) * 2.0 + 3.0
+    dy = th.randn(cap, C, generator=g)
+    live = bn_live(cap, n)
+    bn_floor_rows(x, live)
+    x[live:], dy[live:] = 1e4, -1e4
+    return x, dy, th.rand(C, generator=g) + 0.5, th.randn(C, generator=g), th.randn(C, generator=g), th.rand(C, generator=g) + 0.5
