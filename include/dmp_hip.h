@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 90
+#define DMP_ABI_VERSION 91
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1462,6 +1462,22 @@ int dmp_relconv_fwd(const float *Y, const int32_t *in_ptr, const int32_t *in_ent
 int dmp_relconv_bwd(const float *dOut, const float *out, const int32_t *out_ptr, const int32_t *out_ent, const int32_t *dst32,
                     const int64_t *etype, const float *norm, int64_t N, int R, int loop, int H, int P, int act, float *dY,
                     void *stream);
+
+/* ---- CompGCN's relation-typed weights (dmp_relcorr.hip; UNC Model/CompGCN/src/model.py:117-264, comp_opt "corr") for
+ * dmp_relconv_*: the circular correlation corr(h, t)[k] = sum_i h[i] t[(i + k) mod I] is h @ C(t), C(t)[i, k] = t[(i + k) mod I],
+ * so an edge of type b sends h[src] @ (C(T[b]) @ Win) and the self loop h @ (C(loop_rel) @ Wloop).  T [R, I] (the relation
+ * table of the layer), loop_rel [I], Win / Wloop [I, H], all contiguous fp32; P = H rounded up to 4.  One launch each,
+ * fixed summation order, no atomics.  DMP_ERR_UNSUPPORTED outside dmp_relcorr_supported. */
+/* 1 for 4 <= I, H <= 256 and 2 <= nblk = R + 1 <= 17, else 0. */
+int dmp_relcorr_supported(int I, int H, int nblk);
+/* Wcat [I, (R + 1) P]:  Wcat[i, b P + o] = scale sum_k t_b[(i + k) mod I] W_b[k, o] for o < H, 0 for H <= o < P;
+ * t_b = T[b], W_b = Win for b < R;  t_R = loop_rel, W_R = Wloop. */
+int dmp_relcorr_weights_fwd(const float *T, const float *loop_rel, const float *Win, const float *Wloop, int R, int I, int H, int P,
+                            float scale, float *Wcat, void *stream);
+/* dT [R, I]:  dT[b, j] = scale sum_{i, o} dWcat[i, b P + o] Win[(j - i) mod I, o];  dWin [I, H]:  dWin[k, o] = scale sum_{b < R}
+ * sum_i T[b, (i + k) mod I] dWcat[i, b P + o];  dloop_rel [I] and dWloop [I, H]: the same for block R with loop_rel, Wloop. */
+int dmp_relcorr_weights_bwd(const float *dWcat, const float *T, const float *loop_rel, const float *Win, const float *Wloop, int R, int I,
+                            int H, int P, float scale, float *dT, float *dloop_rel, float *dWin, float *dWloop, void *stream);
 
 #ifdef __cplusplus
 }
