@@ -15,7 +15,7 @@ c_double = ctypes.c_double
 c_ptr = ctypes.c_void_p
 c_size = ctypes.c_size_t
 
-ABI_VERSION = 91
+ABI_VERSION = 92
 
 # ---- limits of the header that the host side relies on (``#define``s of the same names)
 DMP_COLLATE_MAX_JOBS = 4
@@ -128,6 +128,10 @@ class dmp_head_grads(ctypes.Structure):
 class dmp_typed_job(ctypes.Structure):
     _fields_ = [("Hin", c_ptr), ("ldh", c_i64), ("W2", c_ptr), ("ldw", c_i64), ("w_in_out", c_int), ("bias", c_ptr), ("R", c_ptr),
                 ("ldr", c_i64), ("R2", c_ptr), ("ldr2", c_i64), ("act", c_int), ("slope", c_f32), ("out", c_ptr), ("ldo", c_i64)]
+
+
+class dmp_chain_panel(ctypes.Structure):
+    _fields_ = [("W", c_ptr), ("ld", c_i64), ("transposed", c_int)]
 
 
 class dmp_atb2_job(ctypes.Structure):
@@ -318,6 +322,13 @@ SIGNATURES = {
     "dmp_bwd_h1_w_blocks": (c_i64, [c_i64]),
     "dmp_bwd_h1_w": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64,
                              c_ptr, c_ptr, c_ptr, c_ptr]),
+    "dmp_node_chain_blocks": (c_i64, [c_i64]),
+    "dmp_node_chain_panel_words": (c_i64, []),
+    "dmp_node_chain_pack": (c_int, [_p(dmp_chain_panel), c_int, c_ptr, c_ptr]),
+    "dmp_node_chain_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_f32, c_ptr, c_ptr, c_i64, c_i64, c_int,
+                                   c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+    "dmp_node_chain_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_int, c_f32, c_ptr, c_ptr, c_i64, c_i64, c_int,
+                                   c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     "dmp_row_mask_bits": (c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
     "dmp_row_mask_rows": (c_int, [c_ptr, c_i64, c_int, c_i64, c_ptr, c_ptr]),
     "dmp_bwd_z_fused": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,

@@ -844,6 +844,85 @@ def bwd_h1_typed(d_o, W2, h1, tiles, slope=0.0, out=None):
     return d_g, reduce_partials(part), reduce_partials(part_rows)
 
 
+USE_NODE_CHAIN = True   # a layer's node side over the kept nodes' tiles as one launch per pass (csrc/dmp_nodechain.hip) instead of three
+
+
+def node_chain_ok(H, *tensors):
+    """``node_chain_fwd`` / ``node_chain_bwd`` apply: H = 128, the bf16x6 arithmetic, fp32 operands with unit column stride in rows of
+    whole 16-byte pieces, arrays below 4 GiB.  Otherwise the three-launch chain (``typed_jobs`` / ``out_fwd_typed`` / ``bwd_h1_typed``) runs."""
+    if not USE_NODE_CHAIN or H != 128 or _lib.load().dmp_dev_get_exact_fp32():
+        return False
+    lim = (1 << 32) - 65536
+    for a in tensors:
+        if a is None:
+            continue
+        if (a.dtype != torch.float32 or a.dim() != 2 or a.stride(1) != 1 or a.stride(0) % 4 or a.stride(0) * 4 > 16383
+                or a.data_ptr() % 16 or a.size(0) * a.stride(0) * 4 >= lim):
+            return False
+    return True
+
+
+def node_chain_panels(Bn, Wx, nW2):
+    """``(forward panels, backward panels)``: the six weight panels of each pass of a layer's node side as bf16 pieces in the kernel's
+    fragment order (``dmp_node_chain_pack``: one launch for both; made once per layer and step, beside the parameter fold, not per
+    workgroup).  Forward: Wx1, Wx2, Wx0, Bn_in, Bn_out, W2^T; backward: W2, Bn_in^T, Bn_out^T, Wx0^T, Wx1^T, Wx2^T."""
+    lib = _lib.load()
+    H = Bn.size(1)
+    Bn, Wx, nW2 = Bn.detach(), Wx.detach(), nW2.detach()
+    _lib.require_gpu(Bn, Wx, nW2)
+    if not (Bn.is_contiguous() and Wx.is_contiguous() and nW2.is_contiguous()):
+        raise _lib.DmpError("node_chain_panels: contiguous weights expected")
+    words = int(lib.dmp_node_chain_panel_words())
+    out = torch.empty(12 * words, dtype=torch.int32, device=Bn.device)
+    e = Bn.element_size()
+    spec = [(Wx.data_ptr() + H * e, 3 * H, 0), (Wx.data_ptr() + 2 * H * e, 3 * H, 0), (Wx.data_ptr(), 3 * H, 0),
+            (Bn.data_ptr(), H, 0), (Bn.data_ptr() + H * H * e, H, 0), (nW2.data_ptr(), H, 1),
+            (nW2.data_ptr(), H, 0), (Bn.data_ptr(), H, 1), (Bn.data_ptr() + H * H * e, H, 1),
+            (Wx.data_ptr(), 3 * H, 1), (Wx.data_ptr() + H * e, 3 * H, 1), (Wx.data_ptr() + 2 * H * e, 3 * H, 1)]
+    J = (_abi.dmp_chain_panel * len(spec))()
+    for j, (w, ld, tr) in zip(J, spec):
+        j.W, j.ld, j.transposed = w, ld, tr
+    check(lib.dmp_node_chain_pack(J, len(spec), ptr(out), stream_ptr()), "dmp_node_chain_pack")
+    return out[:6 * words], out[6 * words:]
+
+
+def node_chain_fwd(x, S, panels, bn, b2, residual, slope, tiles, H1n, P, xn):
+    """The forward node side of a layer for the rows of ``tiles`` in ONE launch (``dmp_node_chain_fwd``): ``H1n = act(x Wx0 + S_in Bn_in
+    + S_out Bn_out + bn)``, ``P = [x Wx1 | x Wx2]``, ``xn = x + H1n W2^T + b2`` (``residual`` false: without x).  ``S`` [R, >= 2H] =
+    [S_in | S_out], ``P`` [R, >= 2H]; any row strides (column blocks of wider buffers).  ``panels``: ``node_chain_panels(...)[0]``.
+    Rows outside the tiles are neither read nor written."""
+    lib = _lib.load()
+    slot, _, num_tiles, bound = tiles
+    R, H = x.shape
+    _lib.require_gpu(x, S, panels, bn, b2, H1n, P, xn)
+    # (the record form of the launches this one replaces: bench.py prices the names it knows at the kept rows -- 6 arrays here, 7 moved)
+    with _lib.timed("out_fwd_typed[H=%d,R=%d,jobs=2]", (H, R), 4 * H * R * 6):
+        check(lib.dmp_node_chain_fwd(ptr(x), x.stride(0), ptr(S), S.stride(0), ptr(panels), ptr(bn), ptr(b2), int(bool(residual)), float(slope),
+                                     ptr(slot), ptr(num_tiles), bound, R, H, ptr(H1n), H1n.stride(0), ptr(P), P.stride(0), ptr(xn), xn.stride(0),
+                                     stream_ptr()), "dmp_node_chain_fwd")
+    return H1n, P, xn
+
+
+def node_chain_bwd(dxn, H1n, dP, panels, residual, slope, tiles, dPn, dS, dx=None):
+    """The backward node side of a layer for the rows of ``tiles`` in ONE launch (``dmp_node_chain_bwd``): ``dPn = act'(H1n) (.) (dxn W2)``,
+    ``dS = [dPn Bn_in^T | dPn Bn_out^T]``, ``dx = dxn + dPn Wx0^T + dP[:, :H] Wx1^T + dP[:, H:] Wx2^T`` (``residual`` false: without dxn;
+    ``dx`` None: not formed, ``dP`` not read).  Returns ``(column sums of dPn, column sums of the kept rows of dxn)`` as
+    ``bwd_h1_typed`` does (``reduce_partials``: deferred inside ``deferred_reductions``).  ``panels``: ``node_chain_panels(...)[1]``."""
+    lib = _lib.load()
+    slot, _, num_tiles, bound = tiles
+    R, H = dxn.shape
+    _lib.require_gpu(dxn, H1n, dP, panels, dPn, dS, dx)
+    G = int(lib.dmp_node_chain_blocks(bound))
+    part = torch.empty((G, H), dtype=torch.float32, device=dxn.device)
+    part_rows = torch.empty_like(part)
+    with _lib.timed("out_fwd_typed[H=%d,R=%d,jobs=2]", (H, R), 4 * H * R * 6):
+        check(lib.dmp_node_chain_bwd(ptr(dxn), dxn.stride(0), ptr(H1n), H1n.stride(0), ptr(dP), dP.stride(0) if dP is not None else 2 * H,
+                                     ptr(panels), int(bool(residual)), float(slope), ptr(slot), ptr(num_tiles), bound, R, H,
+                                     ptr(dPn), dPn.stride(0), ptr(dS), dS.stride(0), ptr(dx), dx.stride(0) if dx is not None else H,
+                                     ptr(part), ptr(part_rows), stream_ptr()), "dmp_node_chain_bwd")
+    return reduce_partials(part), reduce_partials(part_rows)
+
+
 def h1w_ok(d_o, h1, H):
     """The one-launch form of ``bwd_h1_typed`` + ``atb_typed(plain=True)`` applies: H = 128, the bf16x6 arithmetic, arrays below 4 GiB."""
     lib = _lib.load()
@@ -1714,6 +1793,7 @@ class _FusedDMPLayer(torch.autograd.Function):
             nd = None          # (the backward's row masks start at a table's first node)
         # ---- node side (dmpnn.py:113,121,125 + fn.sum + 129-140)
         S0 = M0 = tables = None
+        chained, chain_panels = False, None
         if l0 is not None:     # sum of z over a node's edges = (sum of the label codes) W0
             enc0, K0 = l0.enc, l0.K
             tables = l0.tables(z.size(0), N)
@@ -1787,12 +1867,22 @@ class _FusedDMPLayer(torch.autograd.Function):
             # that adds them up, the two gathered projection blocks, xn = x + (H1n W2^T + b2) -- nothing is read or written
             # for the other nodes
             T = nd.tiles
-            XP = dead_rows_buffer((N, 3 * H), z.device)          # [x Wx0 + bn (a partial) | P_dst | P_src]
-            T1 = dead_rows_buffer((N, H), z.device)
             H1n = dead_rows_buffer((N, H), z.device)
-            typed_jobs([dict(a=x, W=Wx[:, :H], bias=bn, out=XP[:, :H]), dict(a=S[:, :H], W=Bn[:H], out=T1),
-                        dict(a=x, W=Wx[:, H:2 * H], out=XP[:, H:2 * H]), dict(a=x, W=Wx[:, 2 * H:], out=XP[:, 2 * H:])], T)
-            out_fwd_typed(S[:, H:], Bn[H:], None, XP[:, :H], T, out=H1n, slope=slope, prev2=T1)
+            chained = node_chain_ok(H, x, S, Bn, Wx, nW2)
+            if chained:
+                # ... as ONE launch: the rows stay in the workgroup, the six panels stream through LDS (csrc/dmp_nodechain.hip) --
+                # the partial products x Wx0 + bn and S_in Bn_in never go through memory
+                PX = dead_rows_buffer((N, 2 * H), z.device)      # [P_dst | P_src]
+                # (an INNER layer's xn: the dead rows stay unwritten; the last layer's rows go to the caller: zeros there)
+                xn = dead_rows_buffer((N, H), z.device) if (inner & 1) else torch.zeros((N, H), dtype=torch.float32, device=z.device)
+                chain_panels = node_chain_panels(Bn, Wx, nW2)    # (both passes' panels: one launch per layer and step)
+                node_chain_fwd(x, S, chain_panels[0], bn, nb2, residual, slope, T, H1n, PX, xn)
+            else:
+                XP = dead_rows_buffer((N, 3 * H), z.device)          # [x Wx0 + bn (a partial) | P_dst | P_src]
+                T1 = dead_rows_buffer((N, H), z.device)
+                typed_jobs([dict(a=x, W=Wx[:, :H], bias=bn, out=XP[:, :H]), dict(a=S[:, :H], W=Bn[:H], out=T1),
+                            dict(a=x, W=Wx[:, H:2 * H], out=XP[:, H:2 * H]), dict(a=x, W=Wx[:, 2 * H:], out=XP[:, 2 * H:])], T)
+                out_fwd_typed(S[:, H:], Bn[H:], None, XP[:, :H], T, out=H1n, slope=slope, prev2=T1)
         elif l0 is not None and node_pass:
             pass
         elif l0 is not None and l0.venc is not None:     # x Wx = venc (WV0 Wx): three column blocks of K-column products
@@ -1802,13 +1892,15 @@ class _FusedDMPLayer(torch.autograd.Function):
                 smallk_embed(l0.venc[n0:n1, :VK], MV[t * VK:(t + 1) * VK], None, XP[n0:n1], H)
         else:
             XP = x @ Wx
-        if l0 is not None and node_pass:
+        if (l0 is not None and node_pass) or chained:
             PXr, ldpx = PX, 2 * H                # the gathered projections [P_dst | P_src]
         else:
             PXr, ldpx = XP[:, H:], 3 * H
             if l0 is not None or nd is None:
                 H1n = add_bias_relu_(SB, XP[:, :H], bn, slope)
-        if nd is not None:
+        if chained:
+            pass
+        elif nd is not None:
             # (an INNER layer's xn is read by the next layer of this rep-net only, under the same gate: the dead rows stay
             # unwritten; the last layer's rows go to the caller: zeros there)
             xn = dead_rows_buffer((N, H), z.device) if (inner & 1) else torch.zeros((N, H), dtype=torch.float32, device=z.device)
@@ -1875,6 +1967,7 @@ class _FusedDMPLayer(torch.autograd.Function):
         ctx.vpool, ctx.epool = vpool, epool
         ctx.inner = int(inner)
         ctx.nd = nd
+        ctx.chain_panels = chain_panels
         ctx.l0, ctx.l0_S0, ctx.l0_tables = l0, S0, tables
         ctx.l0_W = None if l0 is None else (W0.detach(), None if WV0 is None else WV0.detach())
         ctx.save_for_backward(x, z if l0 is None else None, S, H1n, H1e, Bn, Wx, Wes, nW2, eW2)
@@ -2049,7 +2142,19 @@ class _FusedDMPLayer(torch.autograd.Function):
             one_launch = onepanel_ok(H) and atb_ok(dxn, H1n) and atb_ok(x, dXP) and (l0 is not None or atb_ok(S, dXP))
             if nd is not None and not (one_launch and binary_gate_mask(ctx.v_gate) is not None):
                 raise _lib.DmpError("fused layer backward: the kept-node path needs the masked weight-gradient launch")
-            if nd is not None:
+            chained = (nd is not None and l0 is None and ctx.chain_panels is not None
+                       and node_chain_ok(H, dxn, H1n, dXP))
+            dx = None
+            if chained:
+                # the kept-node chain as ONE launch (csrc/dmp_nodechain.hip): dPn with its two column sums, dS = dPn Bn^T and
+                # dx = dxn + dXP Wx^T -- the partial products of dx never go through memory.  A dead node's dx row: left unwritten
+                # where the layer before is the only reader (``inner`` bit 1), zeros for whoever made the first layer's rows
+                dPn = dXP[:, :H]
+                dS = dead_rows_buffer((N, 2 * H), x.device)
+                if ctx.needs_input_grad[3]:
+                    dx = dead_rows_buffer((N, H), x.device) if (ctx.inner & 2) else torch.zeros((N, H), dtype=torch.float32, device=x.device)
+                dbn, db2n = node_chain_bwd(dxn, H1n, dXP[:, H:], ctx.chain_panels[1], ctx.residual, slope, nd.tiles, dPn, dS, dx)
+            elif nd is not None:
                 # dPn = act'(H1n) (.) (dxn W2) on the kept nodes' tiles; db2n = the column sums of the dxn rows it fetches
                 dPn, dbn, db2n = bwd_h1_typed(dxn, nW2, H1n, nd.tiles, slope, out=dXP[:, :H])
                 if vcodes:
@@ -2115,7 +2220,9 @@ class _FusedDMPLayer(torch.autograd.Function):
                 else:
                     dWx = wg(x, dXP)
             else:
-                if nd is not None:     # dS = dPn Bn^T on the kept nodes' tiles; the edge kernel reads a dead node's rows as zeros
+                if chained:
+                    pass
+                elif nd is not None:     # dS = dPn Bn^T on the kept nodes' tiles; the edge kernel reads a dead node's rows as zeros
                     dS = dead_rows_buffer((N, 2 * H), x.device)
                     jobs = [dict(a=dPn, W=Bn[:H], w_in_out=False, out=dS[:, :H]), dict(a=dPn, W=Bn[H:], w_in_out=False, out=dS[:, H:])]
                     if ctx.needs_input_grad[3]:    # ... and in the same launch two of the three partial products of dx = dxn + dXP Wx^T
@@ -2142,8 +2249,9 @@ class _FusedDMPLayer(torch.autograd.Function):
                 else:
                     dBn = wg(S, dPn)                                         # [2H,H]
                     dWx = wg(x, dXP)                                         # [H,3H] = [dA_n | dPd | dPs]
-            dx = None
-            if ctx.needs_input_grad[3] and nd is not None:
+            if chained:
+                pass
+            elif ctx.needs_input_grad[3] and nd is not None:
                 # dx = dxn + dXP Wx^T on the kept nodes' tiles: the third 128-deep block of the contraction + the two partial
                 # products made beside dS.  A dead node's row is multiplied by the gate's zero further down: left unwritten
                 # where the layer before is the only reader (``inner`` bit 1), zeros for whoever made the first layer's rows

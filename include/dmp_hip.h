@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 91
+#define DMP_ABI_VERSION 92
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1205,6 +1205,39 @@ int64_t dmp_bwd_h1_w_blocks(int64_t tiles_bound);
 int dmp_bwd_h1_w(const float *dO, int64_t ldo, const float *W2, int64_t ldw, const float *H1, int64_t ldh,
                  const int32_t *slot_edge, const int32_t *num_tiles, int64_t tiles_bound, int64_t E, int H, float slope,
                  float *dG, int64_t ldg, float *partial, float *partial_rows, float *partial_w, void *stream);
+
+/*
+ * The node side of a layer over the kept nodes' tiles (dmp_kept_rows(tiles = 1)) as ONE launch per pass (csrc/dmp_nodechain.hip;
+ * SubgraphCountingMatching/models/dmpnn.py:113,121,125,129-140 over the folded weights): the rows stay in a 512-thread workgroup
+ * (128 rows at a time: operand as bf16 pieces in LDS, the [128, 128] result block in registers), the six weight panels stream
+ * through LDS -- what dmp_out_fwd_typed / dmp_bwd_h1_typed do as three dependent launches with partial sums through memory.
+ *   dmp_node_chain_pack   the panels as bf16 pieces in fragment order, once per step: panel j is B[k][c] = W[k * ld + c], or with
+ *                         `transposed` W[c * ld + k]; out [num_panels * dmp_node_chain_panel_words()] (num_panels <= 12)
+ *   dmp_node_chain_fwd    panels (in this order) Wx1, Wx2, Wx0, Bn_in, Bn_out, W2^T ([in, out] each); S [rows, lds >= 2H] = [S_in | S_out]:
+ *                           P[r] = [x[r] Wx1 | x[r] Wx2]  (P [rows, ldp >= 2H]),   H1n[r] = act(x[r] Wx0 + S_in[r] Bn_in + S_out[r] Bn_out + bn),
+ *                           xn[r] = (residual ? x[r] : 0) + H1n[r] W2^T + b2
+ *   dmp_node_chain_bwd    panels W2, Bn_in^T, Bn_out^T, Wx0^T, Wx1^T, Wx2^T ([k, column] each; the first three suffice when dx is NULL):
+ *                           dPn[r] = act'(H1n[r]) (.) (dxn[r] W2),   dS[r] = [dPn[r] Bn_in^T | dPn[r] Bn_out^T]  (dS [rows, lds >= 2H]),
+ *                           dx[r] = (residual ? dxn[r] : 0) + dPn[r] Wx0^T + dP[r, :H] Wx1^T + dP[r, H:] Wx2^T    (dx NULL: skipped);
+ *                           partial / partial_rows [dmp_node_chain_blocks(tiles_bound), H]: column sums of dPn / of the fetched dxn
+ *                           rows per workgroup, summed by dmp_reduce_partials
+ * for the rows r of the tile list (slot [tiles_bound * 32], -1 = padding; *num_tiles tiles used); the other rows are neither read nor
+ * written.  Fixed summation order: a launch repeats bit for bit.  H = 128, bf16x6, arrays below 4 GiB; DMP_ERR_UNSUPPORTED otherwise
+ * (callers run the three-launch chain).
+ */
+typedef struct {
+  const float *W; int64_t ld; int transposed;
+} dmp_chain_panel;
+int64_t dmp_node_chain_blocks(int64_t tiles_bound);
+int64_t dmp_node_chain_panel_words(void);
+int dmp_node_chain_pack(const dmp_chain_panel *panels, int num_panels, uint32_t *out, void *stream);
+int dmp_node_chain_fwd(const float *x, int64_t ldx, const float *S, int64_t lds, const uint32_t *panels, const float *bn, const float *b2,
+                       int residual, float slope, const int32_t *slot, const int32_t *num_tiles, int64_t tiles_bound, int64_t rows, int H,
+                       float *H1n, int64_t ldh, float *P, int64_t ldp, float *xn, int64_t ldxn, void *stream);
+int dmp_node_chain_bwd(const float *dxn, int64_t ldd, const float *H1n, int64_t ldh, const float *dP, int64_t ldp, const uint32_t *panels,
+                       int residual, float slope, const int32_t *slot, const int32_t *num_tiles, int64_t tiles_bound, int64_t rows, int H,
+                       float *dPn, int64_t ldn, float *dS, int64_t lds, float *dx, int64_t ldx, float *partial, float *partial_rows,
+                       void *stream);
 
 /*
  * Input gradient of the edge chain in one pass (replaces dmp_gather_select + the K=2H GEMM):
