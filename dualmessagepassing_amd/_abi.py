@@ -15,7 +15,7 @@ c_double = ctypes.c_double
 c_ptr = ctypes.c_void_p
 c_size = ctypes.c_size_t
 
-ABI_VERSION = 92
+ABI_VERSION = 93
 
 # ---- limits of the header that the host side relies on (``#define``s of the same names)
 DMP_COLLATE_MAX_JOBS = 4
@@ -329,6 +329,8 @@ SIGNATURES = {
                                    c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     "dmp_node_chain_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_int, c_f32, c_ptr, c_ptr, c_i64, c_i64, c_int,
                                    c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    "dmp_edge_mlp_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_i64,
+                                 c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     "dmp_row_mask_bits": (c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
     "dmp_row_mask_rows": (c_int, [c_ptr, c_i64, c_int, c_i64, c_ptr, c_ptr]),
     "dmp_bwd_z_fused": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,

@@ -812,17 +812,69 @@ def out_fwd_typed_codes(h1, W2t, b2, enc, K, Wc, tiles, prev=None, out=None, w_i
     return out
 
 
-def out_fwd_typed(h1, W2t, b2, prev, tiles, out=None, w_in_out=True, slope=None, prev2=None):
+def out_fwd_typed(h1, W2t, b2, prev, tiles, out=None, w_in_out=True, slope=None, prev2=None, first=None):
     """``prev + (h1 W2^T + b2)`` for the rows of ``tiles`` (``live_tiles``: the edges a 0 / 1 gate keeps, gate 1 there; or
     ``NodeRows.tiles``: the kept nodes); the other rows of the result are not written (``dead_rows_buffer``).  ``W2t`` [in, out]
     (any row stride: a column block of a wider matrix), or with ``w_in_out=False`` the Linear's own [out, in].  ``out``: the
     destination (may be ``prev``: a product accumulates onto its own output); ``prev2``: a second addend; ``slope``:
-    LeakyReLU(slope) on the result."""
+    LeakyReLU(slope) on the result.
+    ``first``: ``h1`` does not exist yet -- the keyword arguments of the edge MLP's first Linear (``z, Wes, P, ldp, bias, coef, index,
+    slope, sel`` of ``edge_fwd_typed``) whose output it is: both Linears then run as ONE launch over the class tiles ``tiles``
+    (``edge_mlp_fwd``), which fills ``h1`` on the way (no ``prev2``, no activation on the result)."""
     R, H = h1.shape
     if out is None:
         out = dead_rows_buffer((R, H), h1.device)
+    if first is not None:
+        if prev2 is not None or slope is not None:
+            raise _lib.DmpError("out_fwd_typed(first=...): neither a second addend nor an activation on the result")
+        edge_mlp_fwd(first["z"], first["Wes"], first["P"], first["ldp"], first["bias"], first["coef"], first["index"], first["slope"],
+                     W2t, b2, prev, tiles, sel=first.get("sel"), w_in_out=w_in_out, h1=h1, out=out)
+        return out
     typed_jobs([dict(a=h1, W=W2t, bias=b2, prev=prev, prev2=prev2, out=out, w_in_out=w_in_out, slope=slope)], tiles)
     return out
+
+
+USE_EDGE_MLP_FWD = True   # a gated inner layer's edge MLP forward over the kept edges' tiles as one launch (csrc/dmp_edgemlp.hip) instead of two
+
+
+def edge_mlp_fwd_ok(H, *tensors):
+    """``edge_mlp_fwd`` applies: H = 128, the bf16x6 arithmetic, fp32 operands with unit column stride in rows of whole 16-byte pieces,
+    arrays below 4 GiB.  Otherwise the two launches (``edge_fwd_typed`` / ``out_fwd_typed``) run."""
+    if not USE_EDGE_MLP_FWD or H != 128 or _lib.load().dmp_dev_get_exact_fp32():
+        return False
+    lim = (1 << 32) - 65536
+    for a in tensors:
+        if a is None:
+            continue
+        if (a.dtype != torch.float32 or a.dim() != 2 or a.stride(1) != 1 or a.stride(0) % 4 or a.stride(0) * 4 > 16383
+                or a.data_ptr() % 16 or a.size(0) * a.stride(0) * 4 >= lim):
+            return False
+    return True
+
+
+def edge_mlp_fwd(z, Wes, P, ldp, bias, coef, index, slope, W2t, b2, prev, tiles, sel=None, w_in_out=True, h1=None, out=None):
+    """``(H1e, zn)`` of a layer's edge MLP for the edges of ``tiles`` (``live_tiles``: the class tiles of the edges a 0 / 1 gate keeps)
+    in ONE launch (``dmp_edge_mlp_fwd``): ``H1e = act(z W_g + P[a] - P[b] + bias)`` as ``edge_fwd_typed`` makes it and
+    ``zn = prev + (H1e W2t + b2)`` as ``out_fwd_typed`` does, bit for bit -- H1e is stored once and not read back.  Rows outside the
+    tiles are neither read nor written (``dead_rows_buffer``).  ``P``: the gathered projections with leading dimension ``ldp``;
+    ``sel`` as in ``edge_fwd_typed``; ``prev`` None: no residual."""
+    lib = _lib.load()
+    E, H = z.shape
+    slot_edge, tile_scale, num_tiles, bound = tiles
+    if h1 is None:
+        h1 = dead_rows_buffer((E, H), z.device)
+    if out is None:
+        out = dead_rows_buffer((E, H), z.device)
+    Wes = Wes.contiguous()
+    sel_a, sel_b = (sel[0], sel[1]) if sel is not None else index.edge_select(coef)[:2]
+    _lib.require_gpu(z, Wes, P, bias, W2t, b2, prev, h1, out)
+    # (the record form of the first of the two launches this one replaces: bench.py prices the names it knows at the kept rows)
+    with _lib.timed("edge_fwd_typed[H=%d,E=%d]", (H, E), 4 * H * (2 * E + 2 * index.num_nodes) + 12 * E):
+        check(lib.dmp_edge_mlp_fwd(ptr(z), z.stride(0), ptr(Wes), Wes.size(1), ptr(P), ldp, index.num_nodes, ptr(bias), ptr(sel_a), ptr(sel_b),
+                                   ptr(W2t), W2t.stride(0), int(bool(w_in_out)), ptr(b2), ptr(prev), prev.stride(0) if prev is not None else H,
+                                   ptr(slot_edge), ptr(tile_scale), ptr(num_tiles), bound, E, H, float(slope), ptr(h1), h1.stride(0),
+                                   ptr(out), out.stride(0), stream_ptr()), "dmp_edge_mlp_fwd")
+    return h1, out
 
 
 def bwd_h1_typed(d_o, W2, h1, tiles, slope=0.0, out=None):
@@ -1921,12 +1973,25 @@ class _FusedDMPLayer(torch.autograd.Function):
         side.wait("erows" if l0 is not None else "tiles")      # (a layer on the label codes needs the tiles only for its second Linear)
         dead_gate = e_gate if (SKIP_DEAD_ROWS and USE_ROW_MASKS and e_gate is not None and typed_ok(index, H)
                                and gate_row_mask(e_gate) is not None) else None
+        # the one-launch edge MLP stands exactly where the route below is edge_fwd_typed + out_fwd_typed over the kept edges' tiles
+        # (dead == 3 with live_tiles and the folded W2^T): a gated INNER layer whose edge rows are wanted, with its residual
+        mlp_tiles = None
+        if (l0 is None and dead_gate is not None and not sums_only and residual and eW2t is not None and (inner & 1)
+                and zero_rows_gate(e_gate) and edge_mlp_fwd_ok(H, z, PXr, eW2t)):
+            mlp_tiles = live_tiles(index, coef, e_gate)
         if l0 is not None:
             H1e = dead_rows_buffer((z.size(0), H), z.device) if dead_gate is not None else torch.empty((z.size(0), H), dtype=torch.float32, device=z.device)
             for t, rows, _ in tables:
                 if rows[1] > rows[0]:
                     l0_edge_fwd(enc0, K0, M0[t * K0:(t + 1) * K0], PXr, ldpx, be, coef, index, slope, rows, H1e,
                                 mask=gate_row_mask(dead_gate) if dead_gate is not None else None)
+        elif mlp_tiles is not None:
+            # both Linears over the kept edges' class tiles as ONE launch: H1e goes from the first to the second on the chip
+            # (through the second Linear's wrapper, as every E-row Linear + residual launch goes: it fills H1e on the way)
+            H1e = dead_rows_buffer((z.size(0), H), z.device)
+            zn = out_fwd_typed(H1e, eW2t, eb2, z, mlp_tiles,
+                               first=dict(z=z, Wes=Wes, P=PXr, ldp=ldpx, bias=be, coef=coef, index=index, slope=slope,
+                                          sel=None if nd is None else nd.sel))
         elif typed_ok(index, H):
             # (under ``nd`` the projection rows of the dead nodes were never written: their selectors read as zeros)
             H1e = edge_fwd_typed(z, Wes, PXr, ldpx, be, coef, index, slope, dead_gate=dead_gate, sel=None if nd is None else nd.sel)

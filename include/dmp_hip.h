@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 92
+#define DMP_ABI_VERSION 93
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1238,6 +1238,23 @@ int dmp_node_chain_bwd(const float *dxn, int64_t ldd, const float *H1n, int64_t 
                        int residual, float slope, const int32_t *slot, const int32_t *num_tiles, int64_t tiles_bound, int64_t rows, int H,
                        float *dPn, int64_t ldn, float *dS, int64_t lds, float *dx, int64_t ldx, float *partial, float *partial_rows,
                        void *stream);
+
+/*
+ * A layer's edge MLP forward over the kept edges' class tiles (dmp_class_tiles_gated) as ONE launch (csrc/dmp_edgemlp.hip;
+ * SubgraphCountingMatching/models/dmpnn.py:142-156 over the folded weights) -- dmp_edge_fwd_typed AND dmp_out_fwd_typed (one job,
+ * no second addend, no activation on the output):
+ *     H1[e]  = act(Z[e] W_g(e) + P[selA e, 0:H] - P[selB e, H:2H] + bias1),   W_g = W[:, 0:H] + c_g W[:, H:2H]
+ *     out[e] = R[e] + (H1[e] W2 + bias2)          (W2 [in, out] with w2_in_out != 0, nn.Linear's [out, in] otherwise; R NULL: no residual)
+ * for the edges e of the tile list; nothing is read, computed or stored for any other edge.  A 512-thread workgroup per CU: four
+ * waves form H1 as dmp_edge_fwd_typed does and hand every tile on as bf16 pieces in LDS, four waves form `out` from that image as
+ * dmp_out_fwd_typed does -- H1 is stored once (the backward needs it) and never read back.  Both outputs are bit-identical to the
+ * two launches' on every kept row.  H = 128, bf16x6, arrays below 4 GiB; DMP_ERR_UNSUPPORTED otherwise (callers run the two launches).
+ */
+int dmp_edge_mlp_fwd(const float *Z, int64_t ldz, const float *W, int64_t ldw, const float *P, int64_t ldp, int64_t num_nodes,
+                     const float *bias1, const int32_t *selA, const int32_t *selB, const float *W2, int64_t ldw2, int w2_in_out,
+                     const float *bias2, const float *R, int64_t ldr, const int32_t *slot_edge, const float *tile_scale,
+                     const int32_t *num_tiles, int64_t tiles_bound, int64_t num_edges, int H, float slope, float *H1, int64_t ldh,
+                     float *out, int64_t ldo, void *stream);
 
 /*
  * Input gradient of the edge chain in one pass (replaces dmp_gather_select + the K=2H GEMM):
