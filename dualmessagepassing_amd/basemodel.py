@@ -15,7 +15,7 @@ from collections import OrderedDict
 import torch as th
 import torch.nn as nn
 
-from . import ops
+from . import gatememo, ops
 from ._lib import on_input_device
 from .compgcn import CompGCNRepMixin
 from .embed import materialize
@@ -151,7 +151,7 @@ def scalar_filter_gates(jobs):
     _lib.check(lib.dmp_scalar_filter_gates(J, len(jobs), B, present.data_ptr(), off, _lib.stream_ptr()),
                "dmp_scalar_filter_gates")
     for g in gates:
-        g._dmp_binary = True          # exactly 0.0 / 1.0: kernels may treat such a gate as a row mask
+        gatememo.mark(g, binary=True)     # exactly 0.0 / 1.0: kernels may treat such a gate as a row mask
     return gates
 
 

@@ -8,7 +8,7 @@ nodes of graphs 0..i-1, node/edge frames are concatenated, ``batch_num_nodes`` /
 """
 import torch
 
-from . import _abi, _lib
+from . import _abi, _lib, gatememo
 from ._lib import check, ptr, stream_ptr
 from .graph import BatchedGraph
 
@@ -414,5 +414,5 @@ def compact_gated_edges(graph, e_gate, capacity, status):
     g.max_num_edges = int(graph.max_num_edges) + cap // B + 1                # kept edges of a graph + its share of the padding
     g.tiling = ops.graph_tiling(node_off, g.edge_offsets, B, g.max_num_edges)
     g.node_tiling = ops.graph_node_tiling(node_off, g.edge_offsets, B, g.max_num_nodes)
-    gate_c._dmp_dense_gate = True                         # ones but for the padding rows: the masked-row kernels have nothing to skip
+    gatememo.mark(gate_c, dense=True)                     # ones but for the padding rows: the masked-row kernels have nothing to skip
     return CompactedEdges(g, ids[2], gate_c, E, kept)

@@ -24,7 +24,7 @@ projecting node rows first leaves 4 of them and is the same linear map.
 import torch as th
 import torch.nn as nn
 
-from . import ops
+from . import gatememo, ops
 from ._lib import on_input_device
 from .act import init_module, init_weight, map_activation_str_to_layer
 from .constants import (EDGEAGG, EDGEFEAT, NODEAGG, NODEFEAT, OUTDEGREE, REVFLAG)
@@ -328,37 +328,35 @@ def _joint_gates(v_gate, e_gate, np_, ep_, dtype, device):
     """``(vg, eg)``: the union's gates -- ones for the pattern rows, the target's gates for its rows -- with the marks the
     kernels read (0 / 1, wiped input rows).  Memoised on the target's gate tensors (``prefetch_joint_indexes`` makes them
     ahead of the pass, on the side stream)."""
-    owner = e_gate if e_gate is not None else v_gate
-    if owner is None:
+    if v_gate is None and e_gate is None:
         return None, None
-    key = (None if v_gate is None else (v_gate.data_ptr(), v_gate._version), None if e_gate is None else (e_gate.data_ptr(), e_gate._version),
-           np_, ep_, dtype)
-    hit = getattr(owner, "_dmp_joint_gates", None)
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    vg = eg = None
-    if v_gate is not None and e_gate is not None:            # ones for the pattern rows, the gates for the target rows
-        from .collate import concat_pairs
-        vg, eg = concat_pairs([((np_, 1.0), v_gate.reshape(-1).to(dtype), 0), ((ep_, 1.0), e_gate.reshape(-1).to(dtype), 0)])
-    elif v_gate is not None:
-        vg = th.cat([th.ones(np_, dtype=dtype, device=device), v_gate.reshape(-1)])
-    elif e_gate is not None:
-        eg = th.cat([th.ones(ep_, dtype=dtype, device=device), e_gate.reshape(-1)])
-    for made, src in ((vg, v_gate), (eg, e_gate)):           # ones for the pattern rows + a 0 / 1 gate: still 0 / 1
-        if made is not None and getattr(src, "_dmp_binary", False):
-            made._dmp_binary = True
-    if eg is not None:
-        eg._dmp_zero_rows = True         # e's target rows are multiplied by this gate (_gate_concat / the packed codes)
-    if vg is not None:
-        vg._dmp_zero_rows = True         # ... and v's target rows by this one: a gated-out node is a zero row in every layer
-        vg._dmp_ones_prefix = np_        # (its first np_ entries are ones by construction: the pattern's nodes are all kept)
-    if eg is not None and getattr(e_gate, "_dmp_dense_gate", False):
-        eg._dmp_dense_gate = True        # the kept edges of a compacted batch (collate.compact_gated_edges): ones but for the padding
-    try:
-        owner._dmp_joint_gates = (key, vg, eg)
-    except Exception:
-        pass
-    return vg, eg
+
+    def build():
+        vg = eg = None
+        if v_gate is not None and e_gate is not None:            # ones for the pattern rows, the gates for the target rows
+            from .collate import concat_pairs
+            vg, eg = concat_pairs([((np_, 1.0), v_gate.reshape(-1).to(dtype), 0), ((ep_, 1.0), e_gate.reshape(-1).to(dtype), 0)])
+        elif v_gate is not None:
+            vg = th.cat([th.ones(np_, dtype=dtype, device=device), v_gate.reshape(-1)])
+        else:
+            eg = th.cat([th.ones(ep_, dtype=dtype, device=device), e_gate.reshape(-1)])
+        if eg is not None:
+            # ones for the pattern rows + a 0 / 1 gate: still 0 / 1; e's target rows are multiplied by this gate (_gate_concat / the
+            # packed codes); the kept edges of a compacted batch (collate.compact_gated_edges) are ones but for the padding
+            gatememo.mark(eg, binary=gatememo.flag(e_gate, "binary"), zero_rows=True, dense=gatememo.flag(e_gate, "dense"))
+        if vg is not None:
+            # ... and v's target rows by this one: a gated-out node is a zero row in every layer (its first np_ entries are ones
+            # by construction: the pattern's nodes are all kept)
+            gatememo.mark(vg, binary=gatememo.flag(v_gate, "binary"), zero_rows=True, ones_prefix=np_)
+        return vg, eg
+
+    # on the edge gate (the node gate where there is none), per version of BOTH gates: the node gate's goes into the name
+    # (so an entry made for an older version of the node gate, or for other sizes / another dtype, stays until the edge gate's
+    # own version changes, where there used to be one entry at a time: the gates are made once per step)
+    if e_gate is None:
+        return gatememo.memo(v_gate, ("joint_gates", np_, ep_, dtype), (), build)
+    v_own = None if v_gate is None else gatememo.owner(v_gate)
+    return gatememo.memo(e_gate, ("joint_gates", np_, ep_, dtype, None if v_own is None else v_own._version), (v_own,), build)
 
 
 def prefetch_joint_indexes(model, pattern, graph, v_gate, e_gate, pool_kinds=(), skip_rev=True):
@@ -427,7 +425,7 @@ def prefetch_joint_indexes(model, pattern, graph, v_gate, e_gate, pool_kinds=(),
         want_nodes = bool(N >= 4096 and fused.onepanel_ok(H) and fused.USE_NODE_ROWS and fused.USE_PLAIN_ATB and fused.zero_rows_gate(vg) and typed and E > 0)
         want_l0 = bool(typed and fused.SKIP_DEAD_ROWS and fused.USE_ROW_MASKS and fused.USE_L0_ROW_LISTS and len(layers) > 1 and ep_ % 32 == 0
                        and E - ep_ >= fused.L0_LIST_MIN_ROWS and th.is_grad_enabled())
-        want_asc = bool(typed and fused.zero_rows_gate(eg) and fused.USE_PLAIN_ATB and getattr(eg, "_dmp_binary", False))
+        want_asc = bool(typed and fused.zero_rows_gate(eg) and fused.USE_PLAIN_ATB and gatememo.flag(eg, "binary"))
         fused.gate_bundle(ix, vg, eg, want_nodes, (ep_, E) if want_l0 else None, want_asc)
         nd = None
         if N >= 4096 and fused.onepanel_ok(H):
@@ -606,7 +604,7 @@ def _layer0_codes(union, layers, p_v_emb, p_e_emb, g_v_emb, g_e_emb, v_gate, e_g
     with side.fork():
         if l0.venc is not None and v_gate is not None:
             l0.venc_mask = fused.code_row_mask(l0.venc, l0.VK)
-        if e_gate is not None and not getattr(e_gate, "_dmp_dense_gate", False):
+        if e_gate is not None and not gatememo.flag(e_gate, "dense"):
             l0.enc_mask = fused.code_row_mask(l0.enc, l0.K)
     return l0
 

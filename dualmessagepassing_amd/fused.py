@@ -23,12 +23,14 @@ Eligibility (``DMPLayer.fused_ok``): 2-layer MLPs, ReLU, no BatchNorm, bias, no 
 square weights, H % 4 == 0, ``is_reversed`` present, gates without gradient.  Anything else
 takes the modular path (same kernels, torch autograd in between).
 """
+import ctypes as _ctypes
+import os as _os
 import threading
 
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _abi, _lib, ops
+from . import _abi, _lib, gatememo, ops
 from ._lib import check, ptr, stream_ptr
 
 
@@ -183,27 +185,24 @@ def keep_pool_csr(pool, gate):
     shape; same sums, same order (the skipped rows added zeros)."""
     if gate is None or not USE_ROW_MASKS or pool.num_chunks == 0 or gate.numel() == 0:
         return None
-    owner = _gate_owner(gate)
-    if getattr(owner, "_dmp_dense_gate", False) or not getattr(owner, "_dmp_binary", False):
+    own = gatememo.owner(gate)
+    if not gatememo.skips_rows(own, True):
         return None
-    memo = getattr(owner, "_dmp_keep_pool", None)
-    if memo is None or memo[0] != owner._version:
-        memo = (owner._version, {})
-        try:
-            owner._dmp_keep_pool = memo
-        except Exception:
-            return None
-    hit = memo[1].get(id(pool))
-    if hit is not None and hit[0] is pool:
-        return hit[1]
-    lib = _lib.load()
-    V, dev = pool.num_chunks, pool.vptr.device
-    nscr = int(lib.dmp_csr_keep_scratch_words(V))
-    ws = torch.empty(nscr + V + 1 + pool.vent.numel(), dtype=torch.int32, device=dev)
-    row_cnt, kptr, kent = ws[:nscr], ws[nscr:nscr + V + 1], ws[nscr + V + 1:]
-    check(lib.dmp_csr_keep(ptr(pool.vptr), ptr(pool.vent), ptr(gate.reshape(-1)), V, pool.vent.numel(), ptr(row_cnt), ptr(kptr), ptr(kent), stream_ptr()),
-          "dmp_csr_keep")
-    memo[1][id(pool)] = (pool, (kptr, kent))
+    return gatememo.memo(own, ("keep_pool", id(pool)), (pool,), lambda: _csr_keep(pool.vptr, pool.vent, gate, pool.num_chunks), True)
+
+
+def _csr_keep_buffers(rows, entries, device):
+    """``(row counts (scratch), ptr [rows + 1], ent [entries])`` of ``dmp_csr_keep`` / ``dmp_incidence_keep``: one allocation."""
+    nscr = int(_lib.load().dmp_csr_keep_scratch_words(rows))
+    ws = torch.empty(nscr + rows + 1 + entries, dtype=torch.int32, device=device)
+    return ws[:nscr], ws[nscr:nscr + rows + 1], ws[nscr + rows + 1:]
+
+
+def _csr_keep(csr_ptr, csr_ent, gate, rows):
+    """``(ptr, ent)``: the CSR ``(csr_ptr, csr_ent)`` of ``rows`` rows over the entries whose ``gate`` is not zero (``dmp_csr_keep``)."""
+    row_cnt, kptr, kent = _csr_keep_buffers(rows, csr_ent.numel(), csr_ptr.device)
+    check(_lib.load().dmp_csr_keep(ptr(csr_ptr), ptr(csr_ent), ptr(gate.reshape(-1)), rows, csr_ent.numel(), ptr(row_cnt), ptr(kptr),
+                                   ptr(kent), stream_ptr()), "dmp_csr_keep")
     return kptr, kent
 
 
@@ -226,23 +225,19 @@ def pool_weight_sums(pool, weight=None):
     lib = _lib.load()
     if not getattr(pool, "rows_in_order", False):
         raise _lib.DmpError("pool_weight_sums: an index over rows in their own order")
+
+    def build():
+        halves = 2 if pool.flag8 is not None else 1
+        out = torch.empty((pool.num_graphs, halves), dtype=torch.float32, device=pool.offsets.device)
+        w = None if weight is None else weight.reshape(-1).contiguous()
+        check(lib.dmp_pool_weight_sums(ptr(w), ptr(pool.flag8), ptr(pool.offsets), pool.num_graphs, ptr(out), stream_ptr()),
+              "dmp_pool_weight_sums")
+        return out
+
     # (a gate's sums are memoised on the gate per index: dmpnn.prefetch_joint_indexes makes them ahead, on the side stream)
-    owner = None if weight is None else _gate_owner(weight)
-    if owner is not None:
-        memo = getattr(owner, "_dmp_pool_wsums", None)
-        if memo is not None and memo[0] == owner._version and memo[1] is pool:
-            return memo[2]
-    halves = 2 if pool.flag8 is not None else 1
-    out = torch.empty((pool.num_graphs, halves), dtype=torch.float32, device=pool.offsets.device)
-    w = None if weight is None else weight.reshape(-1).contiguous()
-    check(lib.dmp_pool_weight_sums(ptr(w), ptr(pool.flag8), ptr(pool.offsets), pool.num_graphs, ptr(out), stream_ptr()),
-          "dmp_pool_weight_sums")
-    if owner is not None and not weight.requires_grad:
-        try:
-            owner._dmp_pool_wsums = (owner._version, pool, out)
-        except Exception:
-            pass
-    return out
+    if weight is None or weight.requires_grad:
+        return build()
+    return gatememo.memo(weight, "pool_weight_sums", (pool,), build)
 
 
 def pool_rowmap(pool):
@@ -372,10 +367,6 @@ def edge_fwd_typed(z, Wes, P, ldp, bias, coef, index, slope=0.0, dead_gate=None,
     return out
 
 
-import ctypes as _ctypes
-import os as _os
-
-
 def masked_slots(index, coef, gate):
     """The class-tile slot list of ``index`` with the edges under a zero ``gate`` turned into padding (``dmp_mask_slots``), or
     None (no gate, masks off, a gate known to be dense).  For kernels whose streamed rows are ZERO for such edges -- ``dPre``
@@ -383,23 +374,17 @@ def masked_slots(index, coef, gate):
     (shared by the layers of a rep-net) per slot list."""
     if gate is None or not USE_ROW_MASKS:
         return None
-    owner = gate._base if gate._base is not None else gate
-    if owner.data_ptr() != gate.data_ptr() or owner.numel() != gate.numel():
-        owner = gate
-    if getattr(owner, "_dmp_dense_gate", False):
+    own = gatememo.owner(gate)
+    if gatememo.flag(own, "dense", True):
         return None
     slot_edge = index.class_tiles(coef)[0]
-    hit = getattr(owner, "_dmp_masked_slots", None)
-    if hit is not None and hit[0] == owner._version and hit[1] is slot_edge:
-        return hit[2]
-    lib = _lib.load()
-    out = torch.empty_like(slot_edge)
-    check(lib.dmp_mask_slots(ptr(slot_edge), slot_edge.numel(), ptr(gate), gate.numel(), ptr(out), stream_ptr()), "dmp_mask_slots")
-    try:
-        owner._dmp_masked_slots = (owner._version, slot_edge, out)
-    except Exception:
-        pass
-    return out
+
+    def build():
+        out = torch.empty_like(slot_edge)
+        check(_lib.load().dmp_mask_slots(ptr(slot_edge), slot_edge.numel(), ptr(gate), gate.numel(), ptr(out), stream_ptr()), "dmp_mask_slots")
+        return out
+
+    return gatememo.memo(own, "masked_slots", (slot_edge,), build, True)
 
 
 USE_LIVE_TILES = True      # (module attributes, not environment switches: tests flip them; the documented DMP_* switches are listed in DESIGN.md 2)
@@ -412,18 +397,10 @@ def live_tiles(index, coef, gate):
     that LEAVE OUT such edges (``masked_slots`` turns them into padding where every edge needs its slot).  Memoised on the gate."""
     if gate is None or not USE_ROW_MASKS or not USE_LIVE_TILES:
         return None
-    owner = _gate_owner(gate)
-    if getattr(owner, "_dmp_dense_gate", False) or not getattr(owner, "_dmp_binary", False):
+    own = gatememo.owner(gate)
+    if not gatememo.skips_rows(own, True):
         return None
-    hit = getattr(owner, "_dmp_live_tiles", None)
-    if hit is not None and hit[0] == owner._version and hit[1] is index and hit[2] is coef:
-        return hit[3]
-    res = index.class_tiles_gated(coef, gate.reshape(-1))
-    try:
-        owner._dmp_live_tiles = (owner._version, index, coef, res)
-    except Exception:
-        pass
-    return res
+    return gatememo.memo(own, "live_tiles", (index, coef), lambda: index.class_tiles_gated(coef, gate.reshape(-1)), True)
 
 
 def keep_in_csr(index, gate):
@@ -431,25 +408,10 @@ def keep_in_csr(index, gate):
     on the gate (the layers of a rep-net share it), or None."""
     if gate is None or not USE_ROW_MASKS or index.num_edges == 0:
         return None
-    owner = _gate_owner(gate)
-    if getattr(owner, "_dmp_dense_gate", False) or not getattr(owner, "_dmp_binary", False):
+    own = gatememo.owner(gate)
+    if not gatememo.skips_rows(own, True):
         return None
-    hit = getattr(owner, "_dmp_keep_csr", None)
-    if hit is not None and hit[0] == owner._version and hit[1] is index:
-        return hit[2]
-    lib = _lib.load()
-    N, dev = index.num_nodes, index.in_ptr.device
-    nscr = int(lib.dmp_csr_keep_scratch_words(N))
-    ws = torch.empty(nscr + N + 1 + index.in_ent.numel(), dtype=torch.int32, device=dev)
-    row_cnt, keep_ptr, keep_ent = ws[:nscr], ws[nscr:nscr + N + 1], ws[nscr + N + 1:]
-    check(lib.dmp_csr_keep(ptr(index.in_ptr), ptr(index.in_ent), ptr(gate.reshape(-1)), N, index.in_ent.numel(), ptr(row_cnt), ptr(keep_ptr),
-                           ptr(keep_ent), stream_ptr()), "dmp_csr_keep")
-    res = (keep_ptr, keep_ent)
-    try:
-        owner._dmp_keep_csr = (owner._version, index, res)
-    except Exception:
-        pass
-    return res
+    return gatememo.memo(own, "keep_in_csr", (index,), lambda: _csr_keep(index.in_ptr, index.in_ent, gate, index.num_nodes), True)
 
 
 _ZEROS = {}
@@ -498,19 +460,14 @@ def ascending_tiles(gate):
     mask = binary_gate_mask(gate)
     if mask is None:
         return None
-    owner = _gate_owner(gate)
-    hit = getattr(owner, "_dmp_asc_tiles", None)
-    if hit is not None and hit[0] == owner._version:
-        return hit[1]
-    R = gate.numel()
-    lst, cnt = kept_rows(mask, 0, R, tiles=True)
-    bound = (R + 31) // 32
-    res = (lst, const_zeros(bound, mask.device), cnt[1:2], bound)
-    try:
-        owner._dmp_asc_tiles = (owner._version, res)
-    except Exception:
-        pass
-    return res
+
+    def build():
+        R = gate.numel()
+        lst, cnt = kept_rows(mask, 0, R, tiles=True)
+        bound = (R + 31) // 32
+        return lst, const_zeros(bound, mask.device), cnt[1:2], bound
+
+    return gatememo.memo(gate, "ascending_tiles", (), build)
 
 
 def bwd_z_typed(d_pre, ld_pre, Wes, d_s, base, coef, index, WesT=None, base_map=None, gate=None, dead_rows=None, dst=None):
@@ -678,30 +635,22 @@ def gate_row_mask(gate):
     memoised on the gate tensor (a layer's forward and backward, and every layer of a rep-net, share the gate)."""
     if gate is None or not USE_ROW_MASKS:
         return None
-    # the layers hand their kernels reshaped VIEWS of the gate they were given (a new tensor object per layer): the mask
-    # hangs on the tensor the views share (same memory, same version counter), so a rep-net builds it once per step
-    owner = gate._base if gate._base is not None else gate
-    if owner.data_ptr() != gate.data_ptr() or owner.numel() != gate.numel():
-        owner = gate
-    if getattr(owner, "_dmp_dense_gate", False):            # a gate its maker knows to be (almost) all ones: nothing to skip
+    own = gatememo.owner(gate)
+    if gatememo.flag(own, "dense", True):            # a gate its maker knows to be (almost) all ones: nothing to skip
         return None
-    hit = getattr(owner, "_dmp_row_mask", None)
-    if hit is not None and hit[0] == owner._version:
-        return hit[1]
-    lib = _lib.load()
-    R = gate.numel()
-    # (a miss on the caller's stream while index builds are in flight on the side stream: the gate itself may have been
-    # written THERE (dmpnn.prefetch_joint_indexes makes the union's gates inside its fork) -- order this stream behind that
-    # stage before reading it.  The prefetch normally builds this mask too and the call above returns its memo: no wait.)
-    from . import side
-    side.wait("erows")
-    mask = torch.empty(((R + 31) // 32,), dtype=torch.int32, device=gate.device)
-    check(lib.dmp_row_mask_bits(ptr(gate), R, ptr(mask), stream_ptr()), "dmp_row_mask_bits")
-    try:
-        owner._dmp_row_mask = (owner._version, mask)
-    except Exception:
-        pass
-    return mask
+
+    def build():
+        # (a miss on the caller's stream while index builds are in flight on the side stream: the gate itself may have been
+        # written THERE (dmpnn.prefetch_joint_indexes makes the union's gates inside its fork) -- order this stream behind that
+        # stage before reading it.  The prefetch normally builds this mask too and the memo returns it: no wait.)
+        from . import side
+        side.wait("erows")
+        R = gate.numel()
+        mask = torch.empty(((R + 31) // 32,), dtype=torch.int32, device=gate.device)
+        check(_lib.load().dmp_row_mask_bits(ptr(gate), R, ptr(mask), stream_ptr()), "dmp_row_mask_bits")
+        return mask
+
+    return gatememo.memo(own, "row_mask", (), build, True)
 
 
 def code_row_mask(enc, K):
@@ -1004,21 +953,20 @@ USE_MASKED_SUMS = True   # the scatter-adds skip the rows a 0 / 1 edge gate wipe
 
 
 def zero_rows_gate(gate):
-    """``gate`` is 0 / 1 (``_dmp_binary``) AND its maker multiplied the rep-net's input rows by it (``_dmp_zero_rows``, set by
+    """``gate`` is 0 / 1 (``gatememo.mark(binary=)``) AND its maker multiplied the rep-net's input rows by it (``zero_rows=``, set by
     ``dmpnn.joint_rep``: the union's edge rows are ``[pattern rows | gate * target rows]``): every layer's input rows under a
     zero of the gate are zeros -- ``zn = z + gate (...)`` (dmpnn.py:215-277) keeps them so -- and sums over rows may leave
     them out."""
     if gate is None or not USE_MASKED_SUMS or not USE_ROW_MASKS:
         return False
-    owner = _gate_owner(gate)
-    return bool(getattr(owner, "_dmp_binary", False) and getattr(owner, "_dmp_zero_rows", False)
-                and not getattr(owner, "_dmp_dense_gate", False))
+    own = gatememo.owner(gate)
+    return bool(gatememo.skips_rows(own, True) and gatememo.flag(own, "zero_rows", True))
 
 
 def binary_gate_mask(gate):
-    """The row mask of a gate flagged 0 / 1 (``_dmp_binary``, e.g. a ScalarFilter gate), else None: for such a gate the mask says
-    everything the gate says."""
-    if gate is None or not USE_PLAIN_ATB or not getattr(_gate_owner(gate), "_dmp_binary", False):
+    """The row mask of a gate flagged 0 / 1 (e.g. a ScalarFilter gate), else None: for such a gate the mask says everything the
+    gate says."""
+    if gate is None or not USE_PLAIN_ATB or not gatememo.flag(gate, "binary"):
         return None
     return gate_row_mask(gate)
 
@@ -1055,21 +1003,13 @@ def bwd_h1_mfma(d_o, W2, h1, coef=None, index=None, both_halves=True, gate=None,
     return d_g, reduce_partials(part)
 
 
-def _gate_owner(gate):
-    """The tensor a gate's views share (``gate_row_mask``): where its memoised masks and flags hang."""
-    owner = gate._base if gate._base is not None else gate
-    if owner.data_ptr() != gate.data_ptr() or owner.numel() != gate.numel():
-        owner = gate
-    return owner
-
-
 USE_PLAIN_ATB = True
 
 
 def atb_rows(a, b, gate=None, colsum=True):
     """``((gate (.) a)^T b  [M,N],  column sums of gate (.) a  [M] (or None))`` in one MFMA pass over the rows
     (csrc/dmp_atb.hip); M, N multiples of 128 (or of 64).  A Linear's weight and bias gradient with a row gate fused in.
-    A gate flagged as 0 / 1 (``_dmp_binary``: a ScalarFilter gate) is fully expressed by its row mask: the product then runs
+    A gate flagged as 0 / 1 (``gatememo.mark(binary=)``: a ScalarFilter gate) is fully expressed by its row mask: the product then runs
     ungated over the masked-in rows on the bf16 pipe (``dmp_atb_rows_plain``), the column sums as a one-column ``smallk_atb``."""
     lib = _lib.load()
     R, M = a.shape
@@ -1231,135 +1171,88 @@ USE_L0_ROW_LISTS = True
 L0_LIST_MIN_ROWS = 32768       # shorter row ranges (the pattern side) keep the masked form: the list costs two launches
 
 
+def _kept_rows_buffers(R, tiles, device):
+    """``(list, count, scratch)`` of ``dmp_kept_rows`` over ``R`` rows, one allocation: the list (``tiles``: padded to whole 32-row
+    tiles), its count words (rows; ``tiles``: rows, tiles), the kernel's scratch."""
+    cap, ncnt = ((R + 31) // 32 * 32, 2) if tiles else (R, 1)
+    out = torch.empty(cap + ncnt + int(_lib.load().dmp_kept_rows_scratch_words(R)), dtype=torch.int32, device=device)
+    return out[:cap], out[cap:cap + ncnt], out[cap + ncnt:]
+
+
+def kept_rows_name(r0, r1, tiles=False):
+    """The name under which ``kept_rows(mask, r0, r1, tiles)`` hangs on ``mask`` (``gatememo``)."""
+    return ("kept_rows", tiles, r0, r1)           # (False == 0 and True == 1, also as parts of a dict key)
+
+
 def kept_rows(mask, r0, r1, tiles=False):
     """``(list int32 [r1 - r0], count int32 [1])``: the rows of ``[r0, r1)`` (r0 a multiple of 32) whose bit of ``mask`` is set, as
     ids relative to r0, ascending (``dmp_kept_rows``); memoised on the mask tensor (the forward and the backward of a layer
     share it).  ``tiles``: the list padded with -1 to whole 32-row tiles and ``count`` int32 [2] = (rows, tiles): a slot list
     for the tile kernels (``node_tiles``)."""
-    if tiles:
-        return _kept_row_tiles(mask, r0, r1)
-    memo = getattr(mask, "_dmp_kept_rows", None)
-    if memo is None:
-        memo = {}
-        try:
-            mask._dmp_kept_rows = memo
-        except Exception:
-            pass
-    hit = memo.get((r0, r1))
-    if hit is not None:
-        return hit
-    lib = _lib.load()
-    R = r1 - r0
-    out = torch.empty(R + 1 + int(lib.dmp_kept_rows_scratch_words(R)), dtype=torch.int32, device=mask.device)
-    lst, cnt, scratch = out[:R], out[R:R + 1], out[R + 1:]
-    check(lib.dmp_kept_rows(ptr(mask[r0 // 32:]), R, 0, ptr(scratch), ptr(lst), ptr(cnt), stream_ptr()), "dmp_kept_rows")
-    memo[(r0, r1)] = (lst, cnt)
-    return lst, cnt
+    def build():
+        R = r1 - r0
+        lst, cnt, scratch = _kept_rows_buffers(R, tiles, mask.device)
+        check(_lib.load().dmp_kept_rows(ptr(mask[r0 // 32:]), R, int(bool(tiles)), ptr(scratch), ptr(lst), ptr(cnt), stream_ptr()), "dmp_kept_rows")
+        return lst, cnt
 
-
-def _kept_row_tiles(mask, r0, r1):
-    memo = getattr(mask, "_dmp_kept_tiles", None)
-    if memo is None:
-        memo = {}
-        try:
-            mask._dmp_kept_tiles = memo
-        except Exception:
-            pass
-    hit = memo.get((r0, r1))
-    if hit is not None:
-        return hit
-    lib = _lib.load()
-    R = r1 - r0
-    cap = (R + 31) // 32 * 32
-    out = torch.empty(cap + 2 + int(lib.dmp_kept_rows_scratch_words(R)), dtype=torch.int32, device=mask.device)
-    lst, cnt, scratch = out[:cap], out[cap:cap + 2], out[cap + 2:]
-    check(lib.dmp_kept_rows(ptr(mask[r0 // 32:]), R, 1, ptr(scratch), ptr(lst), ptr(cnt), stream_ptr()), "dmp_kept_rows")
-    memo[(r0, r1)] = (lst, cnt)
-    return lst, cnt
+    return gatememo.memo(mask, kept_rows_name(r0, r1, tiles), (), build)
 
 
 USE_GATE_BUNDLE = True      # the index arrays a step derives from its two 0 / 1 gates in three launches instead of ten (``gate_bundle``)
-
-
-def _mask_owner(gate):
-    owner = gate._base if gate._base is not None else gate
-    if owner.data_ptr() != gate.data_ptr() or owner.numel() != gate.numel():
-        owner = gate
-    return owner
 
 
 def gate_bundle(index, v_gate, e_gate, want_nodes=False, l0_range=None, want_ascending=False):
     """What ``gate_row_mask`` (both gates), ``kept_rows`` (the kept nodes' tiles, the first layer's kept target rows, the kept
     edges' ascending tiles) and ``GraphIndex.edge_select_nodes`` build in ten launches of ~5 us -- links of the step's index
     chain, which the first layer waits for -- in THREE: both masks (``dmp_row_mask_bits_jobs``), then every list's block counts
-    and the selectors, then every list's fill (``dmp_kept_rows_jobs``).  Each product lands in the memo its own function looks
-    it up in (same bits: the multi-job kernels are the single ones over ``blockIdx.y``); anything not asked for, or already
-    there, is left to those functions."""
+    and the selectors, then every list's fill (``dmp_kept_rows_jobs``).  Each product is planted in the memo its own function
+    looks it up in (same bits: the multi-job kernels are the single ones over ``blockIdx.y``); anything not asked for, or
+    already there, is left to those functions."""
     if not USE_GATE_BUNDLE or not USE_ROW_MASKS:
         return
     lib = _lib.load()
     todo = []
     for g in (v_gate, e_gate):
-        if g is None or not g.is_cuda or g.dtype != torch.float32:
+        if g is None or not g.is_cuda or g.dtype != torch.float32 or gatememo.flag(g, "dense"):
             return
-        owner = _mask_owner(g)
-        if getattr(owner, "_dmp_dense_gate", False):
-            return
-        hit = getattr(owner, "_dmp_row_mask", None)
-        if hit is None or hit[0] != owner._version:
-            todo.append((g, owner))
+        if gatememo.peek(g, "row_mask") is None:
+            todo.append(g)
     if todo:
         jobs = (_abi.dmp_rowmask_job * len(todo))()
-        masks = []
-        for j, (g, owner) in enumerate(todo):
-            R = g.numel()
-            m = torch.empty(((R + 31) // 32,), dtype=torch.int32, device=g.device)
-            masks.append(m)
-            jobs[j].gate, jobs[j].R, jobs[j].mask = ptr(g), R, ptr(m)
+        masks = [torch.empty(((g.numel() + 31) // 32,), dtype=torch.int32, device=g.device) for g in todo]
+        for j, (g, m) in enumerate(zip(todo, masks)):
+            jobs[j].gate, jobs[j].R, jobs[j].mask = ptr(g), g.numel(), ptr(m)
         check(lib.dmp_row_mask_bits_jobs(jobs, len(todo), stream_ptr()), "dmp_row_mask_bits_jobs")
-        for (g, owner), m in zip(todo, masks):
-            try:
-                owner._dmp_row_mask = (owner._version, m)
-            except Exception:
-                return
+        for g, m in zip(todo, masks):
+            gatememo.plant(g, "row_mask", (), m)
     vmask, emask = gate_row_mask(v_gate), gate_row_mask(e_gate)
     if vmask is None or emask is None:
         return
     N, E = index.num_nodes, index.num_edges
-    lists = []          # (mask view, R, tiles, memo dict, key)
-    if want_nodes and N > 0:
-        memo = vmask.__dict__.setdefault("_dmp_kept_tiles", {})
-        if (0, N) not in memo:
-            lists.append((vmask, N, 1, memo, (0, N)))
+    lists = [(vmask, 0, N, 1)] if want_nodes and N > 0 else []                 # (mask, r0, r1, tiles)
     if l0_range is not None and l0_range[1] > l0_range[0] and l0_range[0] % 32 == 0:
-        memo = emask.__dict__.setdefault("_dmp_kept_rows", {})
-        if tuple(l0_range) not in memo:
-            lists.append((emask[l0_range[0] // 32:], l0_range[1] - l0_range[0], 0, memo, tuple(l0_range)))
+        lists.append((emask, l0_range[0], l0_range[1], 0))
     if want_ascending and E > 0:
-        memo = emask.__dict__.setdefault("_dmp_kept_tiles", {})
-        if (0, E) not in memo:
-            lists.append((emask, E, 1, memo, (0, E)))
-    sel = want_nodes and E > 0 and (getattr(index, "_esel_nodes", None) is None or index._esel_nodes[0] is not vmask)
+        lists.append((emask, 0, E, 1))
+    lists = [l for l in lists if gatememo.peek(l[0], kept_rows_name(*l[1:])) is None]
+    sel = want_nodes and E > 0 and gatememo.peek(index, "edge_select_nodes", (vmask,)) is None
     if not lists and not sel:
         return
     jobs = (_abi.dmp_kept_job * max(len(lists), 1))()
-    keep = []
-    for j, (m, R, tiles, memo, key) in enumerate(lists):
-        cap = (R + 31) // 32 * 32 if tiles else R
-        ncnt = 2 if tiles else 1
-        out = torch.empty(cap + ncnt + int(lib.dmp_kept_rows_scratch_words(R)), dtype=torch.int32, device=m.device)
-        lst, cnt, scratch = out[:cap], out[cap:cap + ncnt], out[cap + ncnt:]
-        jobs[j].mask, jobs[j].R, jobs[j].tiles, jobs[j].scratch, jobs[j].list, jobs[j].count = ptr(m), R, tiles, ptr(scratch), ptr(lst), ptr(cnt)
-        keep.append((memo, key, (lst, cnt)))
+    made = []
+    for j, (m, r0, r1, tiles) in enumerate(lists):
+        lst, cnt, scratch = _kept_rows_buffers(r1 - r0, tiles, m.device)
+        jobs[j].mask, jobs[j].R, jobs[j].tiles, jobs[j].scratch, jobs[j].list, jobs[j].count = ptr(m[r0 // 32:]), r1 - r0, tiles, ptr(scratch), ptr(lst), ptr(cnt)
+        made.append((lst, cnt))
     so = torch.empty((3, E), dtype=torch.int32, device=index.device) if sel else None
     check(lib.dmp_kept_rows_jobs(jobs, len(lists), ptr(index.src32) if sel else None, ptr(index.dst32) if sel else None,
                                  ptr(index.rev8) if sel else None, ptr(vmask) if sel else None, E if sel else 0,
                                  ptr(so[0]) if sel else None, ptr(so[1]) if sel else None, ptr(so[2]) if sel else None, stream_ptr()),
           "dmp_kept_rows_jobs")
-    for memo, key, val in keep:
-        memo[key] = val
+    for (m, r0, r1, tiles), val in zip(lists, made):
+        gatememo.plant(m, kept_rows_name(r0, r1, tiles), (), val)
     if sel:
-        index._esel_nodes = (vmask, (so[0], so[1], so[2]))
+        gatememo.plant(index, "edge_select_nodes", (vmask,), (so[0], so[1], so[2]))
 
 
 USE_NODE_ROWS = _os.environ.get("DMP_NODE_ROWS", "1") == "1"   # the node side of a layer over the nodes a 0 / 1 node gate keeps
@@ -1374,30 +1267,22 @@ class NodeRows:
     def __init__(self, mask, rows, tiles, sel, prefix=0):
         self.mask, self.rows, self.tiles, self.sel = mask, rows, tiles, sel
         self.prefix = int(prefix)     # the first ``prefix`` nodes are all kept (the pattern's nodes of a joint pass): list[q] == q there
-        self._kinc = None
 
     def kept_incidence(self, index, e_gate, in_only=False):
         """``(ptr, ent)``: the incidence CSR over the edges the 0 / 1 ``e_gate`` keeps, one row per POSITION of ``rows``
         (``dmp_incidence_keep``): what the backward's endpoint sums walk -- an edge row without a kept endpoint is never
         fetched.  ``in_only``: the in-entries alone = the kept edges' CSR by destination, a row per position (the forward
-        aggregation).  Memoised per gate (the layers of a rep-net share it)."""
-        owner = _gate_owner(e_gate)
-        memo = self._kinc if self._kinc is not None and self._kinc[0] is owner and self._kinc[1] == owner._version else (owner, owner._version, {})
-        self._kinc = memo
-        hit = memo[2].get(bool(in_only))
-        if hit is not None:
-            return hit
-        lib = _lib.load()
-        N, dev = index.num_nodes, index.in_ptr.device
-        nscr = int(lib.dmp_csr_keep_scratch_words(N))
-        ws = torch.empty(nscr + N + 1 + (1 if in_only else 2) * index.num_edges, dtype=torch.int32, device=dev)
-        row_cnt, kptr, kent = ws[:nscr], ws[nscr:nscr + N + 1], ws[nscr + N + 1:]
-        check(lib.dmp_incidence_keep(ptr(index.in_ptr), ptr(index.in_ent), None if in_only else ptr(index.out_ptr),
-                                     None if in_only else ptr(index.out_ent), ptr(e_gate.reshape(-1)),
-                                     ptr(self.rows[0]), ptr(self.rows[1]), N, ptr(row_cnt), ptr(kptr), ptr(kent), stream_ptr()),
-              "dmp_incidence_keep")
-        memo[2][bool(in_only)] = (kptr, kent)
-        return kptr, kent
+        aggregation).  Memoised on the gate per ``NodeRows`` (the layers of a rep-net share it)."""
+        def build():
+            N = index.num_nodes
+            row_cnt, kptr, kent = _csr_keep_buffers(N, (1 if in_only else 2) * index.num_edges, index.in_ptr.device)
+            check(_lib.load().dmp_incidence_keep(ptr(index.in_ptr), ptr(index.in_ent), None if in_only else ptr(index.out_ptr),
+                                                 None if in_only else ptr(index.out_ent), ptr(e_gate.reshape(-1)),
+                                                 ptr(self.rows[0]), ptr(self.rows[1]), N, ptr(row_cnt), ptr(kptr), ptr(kent), stream_ptr()),
+                  "dmp_incidence_keep")
+            return kptr, kent
+
+        return gatememo.memo(e_gate, ("kept_incidence", bool(in_only)), (self,), build)
 
 
 def node_rows(index, v_gate, H):
@@ -1411,21 +1296,16 @@ def node_rows(index, v_gate, H):
     mask = gate_row_mask(v_gate)
     if mask is None:
         return None
-    owner = _gate_owner(v_gate)
-    hit = getattr(owner, "_dmp_node_rows", None)
-    if hit is not None and hit[0] == owner._version and hit[1] is index:
-        return hit[2]
-    N = index.num_nodes
-    lst, cnt = kept_rows(mask, 0, N, tiles=True)
-    bound = (N + 31) // 32
-    scale = const_zeros(bound, mask.device)
-    res = NodeRows(mask, (lst, cnt[0:1]), (lst, scale, cnt[1:2], bound), index.edge_select_nodes(mask),
-                   prefix=min(int(getattr(owner, "_dmp_ones_prefix", 0)), N))
-    try:
-        owner._dmp_node_rows = (owner._version, index, res)
-    except Exception:
-        pass
-    return res
+
+    def build():
+        N = index.num_nodes
+        lst, cnt = kept_rows(mask, 0, N, tiles=True)
+        bound = (N + 31) // 32
+        scale = const_zeros(bound, mask.device)
+        return NodeRows(mask, (lst, cnt[0:1]), (lst, scale, cnt[1:2], bound), index.edge_select_nodes(mask),
+                        prefix=min(int(gatememo.flag(v_gate, "ones_prefix")), N))
+
+    return gatememo.memo(v_gate, "node_rows", (index,), build)
 
 
 # (measured, round 5: LARGE kernels do not gain from the side stream -- the weight-gradient launches of a layer's backward beside its
@@ -1900,7 +1780,7 @@ class _FusedDMPLayer(torch.autograd.Function):
                         SB[n0:n1].addmm_(S0[n0:n1, Kp:Kp + K0], WB[1, t * K0:(t + 1) * K0])
             S = None
         else:
-            # (input rows under a zero of a gate whose maker wiped them -- ``_dmp_zero_rows`` -- are zeros: not fetched)
+            # (input rows under a zero of a gate whose maker wiped them -- ``zero_rows_gate`` -- are zeros: not fetched)
             side.wait("keepcsr")
             kc = keep_in_csr(index, e_gate) if zero_rows_gate(e_gate) else None
             if kc is not None and nd is not None:   # ... and over the kept NODES' rows only: the others' aggregates are dead

@@ -8,7 +8,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     import bench
-    from dualmessagepassing_amd import fused
+    from dualmessagepassing_amd import fused, gatememo
     from dualmessagepassing_amd.collate import collate_device
     from dualmessagepassing_amd.dmpnn import prepare_joint
     dev = th.device("cuda:0")
@@ -31,8 +31,7 @@ def main():
         ds = [th.randn(E, H, device=dev, generator=g) for _ in range(3)]
         for frac in (1.0, 0.42, 0.1):
             gate = (th.rand(E, device=dev, generator=g) < frac).float()
-            gate._dmp_binary = True
-            gate._dmp_zero_rows = True
+            gatememo.mark(gate, binary=True, zero_rows=True)
             gt = gate if frac < 1.0 else None
 
             def timeit(fn, reps=30):

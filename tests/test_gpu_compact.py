@@ -496,7 +496,7 @@ def test_first_layer_residual_rows_from_their_codes_leave_the_model_as_it_was(fi
 def test_binary_gate_weight_gradient_on_the_plain_rows_product(R, M, N):
     """``fused.atb_rows`` with a gate flagged 0 / 1: the ungated product over the masked-in rows (bf16x6) + the one-column
     column sums against fp64 and against the gated f32 form; rows under a zero gate are never fetched (NaN there)."""
-    from dualmessagepassing_amd import fused
+    from dualmessagepassing_amd import fused, gatememo
     gpu = th.device("cuda:0")
     g = th.Generator(device=gpu).manual_seed(R + M)
     gate = (th.rand(R, device=gpu, generator=g) < 0.4).float()
@@ -505,7 +505,7 @@ def test_binary_gate_weight_gradient_on_the_plain_rows_product(R, M, N):
     ref_w = (a.double() * gate.double()[:, None]).t() @ b.double()
     ref_c = (a.double() * gate.double()[:, None]).sum(0)
     w0, c0 = fused.atb_rows(a, b, gate)                           # not flagged: the gated form
-    gate._dmp_binary = True
+    gatememo.mark(gate, binary=True)
     ap, bp = a.clone(), b.clone()
     ap[gate == 0] = float("nan")
     bp[gate == 0] = float("nan")
@@ -519,11 +519,11 @@ def test_binary_gate_weight_gradient_on_the_plain_rows_product(R, M, N):
 
 @pytest.mark.parametrize("H,R", [(128, 40003), (64, 5000)])
 def test_bwd_h1_hands_out_the_gated_column_sums(H, R):
-    from dualmessagepassing_amd import fused
+    from dualmessagepassing_amd import fused, gatememo
     gpu = th.device("cuda:0")
     g = th.Generator(device=gpu).manual_seed(H + R)
     gate = (th.rand(R, device=gpu, generator=g) < 0.4).float()
-    gate._dmp_binary = True
+    gatememo.mark(gate, binary=True)
     d_o = th.randn(R, H, device=gpu, generator=g)
     h1 = th.randn(R, H, device=gpu, generator=g)
     W2 = th.randn(H, H, device=gpu, generator=g) / H ** 0.5
@@ -538,11 +538,11 @@ def test_bwd_h1_hands_out_the_gated_column_sums(H, R):
 def test_rows_jobs_without_gates_run_ungated_over_the_masked_in_rows(R, H):
     """``fused.atb_rows_multi`` whose jobs carry neither a gate nor column sums (the node side of a step under a 0 / 1 gate):
     one bf16x6 launch; rows a job's mask leaves out are never fetched (NaN there), jobs without a mask read every row."""
-    from dualmessagepassing_amd import fused
+    from dualmessagepassing_amd import fused, gatememo
     gpu = th.device("cuda:0")
     g = th.Generator(device=gpu).manual_seed(R + H)
     gate = (th.rand(R, device=gpu, generator=g) < 0.4).float()
-    gate._dmp_binary = True
+    gatememo.mark(gate, binary=True)
     mask = fused.binary_gate_mask(gate)
     assert mask is not None
     a = th.randn(R, H, device=gpu, generator=g)
@@ -625,7 +625,7 @@ def test_masked_endpoint_sums_equal_the_plain_ones_without_reading_zero_rows(H):
 def test_in_csr_over_the_kept_edges(B, max_n, max_e, keep):
     """``dmp_csr_keep``: the CSR by destination restricted to the edges a 0 / 1 gate keeps -- every row's kept entries in their
     order, packed as in the whole CSR -- and the node aggregation over it equals the gate-weighted one bit for bit."""
-    from dualmessagepassing_amd import fused, ops
+    from dualmessagepassing_amd import fused, ops, gatememo
     gpu = th.device("cuda:0")
     rng = np.random.default_rng(B + max_e)
     graph = _random_batch(rng, B, max_n, max_e, gpu)[0]
@@ -633,7 +633,7 @@ def test_in_csr_over_the_kept_edges(B, max_n, max_e, keep):
     E, N = ix.num_edges, ix.num_nodes
     g_np = (rng.random(E) < keep).astype(np.float32)
     gate = th.from_numpy(g_np).to(gpu)
-    gate._dmp_binary = True
+    gatememo.mark(gate, binary=True)
     kc = fused.keep_in_csr(ix, gate)
     if kc is None:
         pytest.skip("DMP_KEEP_CSR / DMP_ROW_MASKS switched off")

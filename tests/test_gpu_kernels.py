@@ -474,7 +474,7 @@ def test_class_tiles_over_the_kept_edges(rows, keep, gpu):
     """``dmp_class_tiles_gated``: the tile list of the edges a 0 / 1 gate keeps -- every kept edge in exactly one slot, no
     other edge anywhere, one class per tile with its scale, classes / nodes / edge ids ascending -- and the three class-typed
     launches over it equal the launches over all edges on the kept rows (rows under a zero gate: never read, NaN there)."""
-    from dualmessagepassing_amd import fused
+    from dualmessagepassing_amd import fused, gatememo
     h = 128
     gen = th.Generator().manual_seed(rows + 11)
     rng = np.random.default_rng(rows + 11)
@@ -486,7 +486,7 @@ def test_class_tiles_over_the_kept_edges(rows, keep, gpu):
     ce = ix.edge_select(coef)[2].cpu().numpy()
     g_np = (rng.random(rows) < keep).astype(np.float32)
     gate = th.from_numpy(g_np).to(gpu)
-    gate._dmp_binary = True
+    gatememo.mark(gate, binary=True)
     slot_edge, tile_scale, num_tiles, bound = ix.class_tiles_gated(coef, gate)
     assert bound == ix.class_tiles(coef)[3]
     nt = int(num_tiles.item())
@@ -537,7 +537,7 @@ def test_second_linear_over_the_kept_edges_tiles(rows, h, gpu):
     """``dmp_out_fwd_typed`` / ``dmp_bwd_h1_typed`` (the kept edges' tiles of a 0 / 1 gate) against the one-panel kernels over
     all rows: equal on the kept rows up to the summation order of the bf16x6 products (same products, same order inside a
     row: equal bits), the other rows untouched, the column sums to fp32 accuracy; rows under a zero gate are never read."""
-    from dualmessagepassing_amd import fused
+    from dualmessagepassing_amd import fused, gatememo
     gen = th.Generator().manual_seed(rows + h)
     rng = np.random.default_rng(rows + h)
     n = max(2, rows // 6)
@@ -545,7 +545,7 @@ def test_second_linear_over_the_kept_edges_tiles(rows, h, gpu):
     ix = _index(src, dst, n, rng.random(rows) < 0.5, gpu)
     coef = ix.degree_coef(ix.out_deg)
     gate = th.from_numpy((rng.random(rows) < 0.46).astype(np.float32)).to(gpu)
-    gate._dmp_binary = True
+    gatememo.mark(gate, binary=True)
     dead = gate == 0
     tiles = fused.live_tiles(ix, coef, gate)
     assert tiles is not None
@@ -582,7 +582,7 @@ def test_second_linear_with_the_residual_rows_from_their_codes(rows, k, kpad, as
     that the [E, H] rows are never in memory) against ``dmp_out_fwd_typed`` reading ``z0`` made in fp64: equal on the kept rows to
     fp32 accuracy (the codes product runs as bf16x6 like the rest), the other rows untouched, rows of h1 under a zero gate and the
     padding columns of the code rows never read (NaN there); the same bits on every launch."""
-    from dualmessagepassing_amd import fused
+    from dualmessagepassing_amd import fused, gatememo
     h = 128
     gen = th.Generator().manual_seed(rows + k)
     rng = np.random.default_rng(rows + k)
@@ -591,7 +591,7 @@ def test_second_linear_with_the_residual_rows_from_their_codes(rows, k, kpad, as
     ix = _index(src, dst, n, rng.random(rows) < 0.5, gpu)
     coef = ix.degree_coef(ix.out_deg)
     gate = th.from_numpy((rng.random(rows) < 0.46).astype(np.float32)).to(gpu)
-    gate._dmp_binary = True
+    gatememo.mark(gate, binary=True)
     dead = gate == 0
     tiles = fused.ascending_tiles(gate) if ascending else fused.live_tiles(ix, coef, gate)
     assert tiles is not None
@@ -632,7 +632,7 @@ def test_second_linear_backward_in_one_launch(rows, ascending, gpu):
     columns, one bf16-piece LDS image per operand read by rows and through ds_read_b64_tr_b16) against the two launches it
     replaces: dPre BIT-identical to ``dmp_bwd_h1_typed`` on the kept rows, the other rows untouched, rows under a zero gate never
     read (NaN there); the two column sums and dO^T H1 to fp32 accuracy against fp64; the same bits on every launch."""
-    from dualmessagepassing_amd import fused
+    from dualmessagepassing_amd import fused, gatememo
     h = 128
     gen = th.Generator().manual_seed(rows)
     rng = np.random.default_rng(rows)
@@ -641,7 +641,7 @@ def test_second_linear_backward_in_one_launch(rows, ascending, gpu):
     ix = _index(src, dst, n, rng.random(rows) < 0.5, gpu)
     coef = ix.degree_coef(ix.out_deg)
     gate = th.from_numpy((rng.random(rows) < 0.46).astype(np.float32)).to(gpu)
-    gate._dmp_binary = True
+    gatememo.mark(gate, binary=True)
     dead = gate == 0
     tiles = fused.ascending_tiles(gate) if ascending else fused.live_tiles(ix, coef, gate)
     assert tiles is not None
@@ -1351,7 +1351,7 @@ def test_tile_list_weight_gradients_on_the_piece_image(rows, gpu):
     ds_read_b64_tr_b16) against fp64 and against the kernels it replaces: ``atb_typed`` ([z^T d | z^T (c (.) d)] over the class
     tiles of the kept edges, and its plain form) and the node side's multi-product launch over a kept-row tile list (operands
     that are column slices); the same bits on every launch."""
-    from dualmessagepassing_amd import fused
+    from dualmessagepassing_amd import fused, gatememo
     h = 128
     gen = th.Generator().manual_seed(rows)
     rng = np.random.default_rng(rows)
@@ -1360,7 +1360,7 @@ def test_tile_list_weight_gradients_on_the_piece_image(rows, gpu):
     ix = _index(src, dst, n, rng.random(rows) < 0.5, gpu)
     coef = ix.degree_coef(ix.out_deg)
     gate = th.from_numpy((rng.random(rows) < 0.46).astype(np.float32)).to(gpu)
-    gate._dmp_binary = True
+    gatememo.mark(gate, binary=True)
     keep = gate != 0
     z = th.randn(rows, h, generator=gen).to(gpu)
     d = th.randn(rows, h, generator=gen).to(gpu)
@@ -1438,7 +1438,7 @@ def test_input_gradient_and_class_typed_weight_gradient_in_one_launch(rows, mapp
     """``dmp_bwd_z_w`` (csrc/dmp_h1w.hip::dzw_k) against the two launches it replaces over the kept edges' class tiles: ``dz`` BIT-identical to
     ``dmp_bwd_z_typed_arow`` on the kept rows (zeros / untouched elsewhere), ``dWes = [z^T dPre | z^T (c dPre)]`` against fp64 and ``atb_typed``;
     NaN in every dead row of every operand; with a base TABLE + row map (the pooled last layer), with dead destinations (-1), and twice the same bits."""
-    from dualmessagepassing_amd import fused
+    from dualmessagepassing_amd import fused, gatememo
     h = 128
     gen = th.Generator().manual_seed(rows + mapped)
     rng = np.random.default_rng(rows)
@@ -1447,8 +1447,7 @@ def test_input_gradient_and_class_typed_weight_gradient_in_one_launch(rows, mapp
     ix = _index(src, dst, n, rng.random(rows) < 0.5, gpu)
     coef = ix.degree_coef(ix.out_deg)
     gate = th.from_numpy((rng.random(rows) < 0.46).astype(np.float32)).to(gpu)
-    gate._dmp_binary = True
-    gate._dmp_zero_rows = True
+    gatememo.mark(gate, binary=True, zero_rows=True)
     dead = gate == 0
     z = th.randn(rows, h, generator=gen).to(gpu)
     wes = (th.randn(h, 2 * h, generator=gen) * 0.1).to(gpu)

@@ -76,15 +76,14 @@ def _batch(gpu, B=96, seed=3):
 def test_scatter_adds_leave_out_the_dead_nodes_rows(H, gpu):
     """Forward sum over a row list / backward one-pass endpoint sums with a node mask: the kept nodes' rows equal the all-rows
     launches bit for bit, a dead node's row is not written (a sentinel survives), NaN in the skipped edge rows never shows."""
-    from dualmessagepassing_amd import fused, ops
+    from dualmessagepassing_amd import fused, ops, gatememo
     ix = _batch(gpu)
     N, E = ix.num_nodes, ix.num_edges
     g = th.Generator(device=gpu).manual_seed(H)
     e_gate = (th.rand(E, device=gpu, generator=g) < 0.42).float()
     v_gate = (th.rand(N, device=gpu, generator=g) < 0.41).float()
     for t in (e_gate, v_gate):
-        t._dmp_binary = True
-        t._dmp_zero_rows = True
+        gatememo.mark(t, binary=True, zero_rows=True)
     M = th.randn(E, H, device=gpu, generator=g) * e_gate[:, None]
     kc = fused.keep_in_csr(ix, e_gate)
     vmask = fused.gate_row_mask(v_gate)
