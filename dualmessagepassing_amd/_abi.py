@@ -15,7 +15,7 @@ c_double = ctypes.c_double
 c_ptr = ctypes.c_void_p
 c_size = ctypes.c_size_t
 
-ABI_VERSION = 93
+ABI_VERSION = 94
 
 # ---- limits of the header that the host side relies on (``#define``s of the same names)
 DMP_COLLATE_MAX_JOBS = 4
@@ -368,4 +368,10 @@ SIGNATURES = {
     "dmp_relcorr_weights_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_f32, c_ptr, c_ptr]),
     "dmp_relcorr_weights_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_ptr,
                                         c_ptr]),
+    "dmp_txl_supported": (c_int, [c_int, c_int, c_int]),
+    "dmp_txl_attn_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_f32, c_ptr, c_ptr, c_ptr,
+                                 c_ptr]),
+    "dmp_txl_bwd_groups": (c_i64, [c_i64, c_int]),
+    "dmp_txl_attn_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_f32,
+                                 c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
 }

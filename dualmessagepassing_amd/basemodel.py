@@ -1081,4 +1081,7 @@ def build_model(config=None, **kw):
     if rep_net == "RNN":
         from .seqmodel import RNN
         return RNN(**config)
+    if rep_net == "TXL":
+        from .seqmodel import TXL
+        return TXL(**config)
     raise NotImplementedError("rep_net=%s is outside the MI355X hot-path scope" % rep_net)

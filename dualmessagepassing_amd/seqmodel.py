@@ -1,12 +1,12 @@
 """The edge-sequence models: ``EdgeSeqModel`` (``SubgraphCountingMatching/models/basemodel.py:222-617``) and its
-rep-nets ``CNN`` (``models/cnn.py``) and ``RNN`` (``models/rnn.py``).
+rep-nets ``CNN`` (``models/cnn.py``), ``RNN`` (``models/rnn.py``) and ``TXL`` (``models/txl.py``).
 
 Same constructor keywords, sub-module names (hence ``state_dict`` keys), initialisers and seeded RNG order as the
 reference, and ``forward(pattern, graph) -> OutputDict`` with its 15 keys (the ``*_v_*`` entries None).  The inputs are
 ``edgeseq.EdgeSeq`` batches.  Activations stay channels-last ``[B, L, H]``: a CNN layer runs either the fused HIP kernels
 of ``cnn.py`` (``cnn.hip_layer_ok``) or the reference's tensor ops on a transposed view, an RNN layer either the recurrence
 kernels of ``rnn.py`` (``rnn.hip_layer_ok``) or its own ``nn.LSTM`` / ``nn.GRU`` / ``nn.RNN``; both compute the same
-function."""
+function.  A TXL layer's attention is ``txl.rel_attention``: the kernels of ``csrc/dmp_txl.hip`` or the same in tensor ops."""
 from collections import OrderedDict
 
 import torch as th
@@ -15,8 +15,9 @@ import torch.nn.functional as F
 
 from . import cnn as _cnn
 from . import rnn as _rnn
+from . import txl as _txl
 from ._lib import on_input_device
-from .act import init_module, map_activation_str_to_layer
+from .act import init_module, init_weight, map_activation_str_to_layer
 from .basemodel import BaseModel, OutputDict, ScalarFilter
 from .constants import REVFLAG
 from .embed import (EquivariantEmbedding, MultihotEmbedding, NormalEmbedding, OrthogonalEmbedding, PositionEmbedding,
@@ -394,4 +395,127 @@ class RNN(EdgeSeqModel):
         return self._rep(self.g_rep_net, g_emb * g, g.view(g_emb.size(0), -1), self.rep_residual)
 
 
-SEQ_MODELS = {"CNN": CNN, "RNN": RNN}
+class TXL(EdgeSeqModel):
+    """txl.py:212-383 (``TransformerXL``), as the reference computes it:
+
+    * keywords ``seg_len`` (64), ``mem_len`` (64), ``clamp_len`` (-1), ``num_heads`` (1), ``pre_lnorm`` (False) are read bare;
+      ``ext_len`` is read from ``seg_len`` too (default 0).  Hence two memory regimes.  ``seg_len`` not passed: ``ext_len = 0`` and
+      layer i of a segment also attends the previous segment's input to layer i (detached; ``klen = mem_len + seg_len`` from
+      the second segment on).  ``seg_len`` passed: ``ext_len = seg_len``, the memory stays empty and every segment is attended
+      on its own; the segments are then independent and ``fold_segments`` runs them as one batch ``[B S, seg_len, H]``;
+    * the sequence is padded to a multiple of ``seg_len`` AFTER its rows, the mask BEFORE them, and the result is the last L
+      rows: with padding, data, mask and output are offset by the pad;
+    * nothing is masked inside the attention (padding rows and zeroed memory rows are attended); the mask zeroes every
+      layer's output rows;
+    * ``init_mems`` makes ``len(rep_net) + 1 = 4`` memories, so more than 4 layers fail; they are refused at construction."""
+
+    MAX_LAYERS = 4          # len(RepNetDict) + 1 memories, layer i reads memory i
+
+    def __init__(self, **kw):
+        self.seg_len = kw.get("seg_len", 64)
+        self.ext_len = kw.get("seg_len", 0)
+        self.mem_len = kw.get("mem_len", 64)
+        self.clamp_len = kw.get("clamp_len", -1)
+        self.max_len = self.seg_len + self.ext_len + self.mem_len
+        self.num_heads = kw.get("num_heads", 1)
+        self.fold_segments = True
+        super(TXL, self).__init__(**kw)
+        self.pos_emb = PositionEmbedding(self.hid_dim, max_len=max(self.clamp_len, self.max_len))
+        self.pos_emb.weight.requires_grad = False
+        self.drop = nn.Dropout(kw.get("rep_dropout", 0.0))
+
+    def create_rep_net(self, type, **kw):
+        if type == "graph":
+            num_layers = kw.get("rep_num_graph_layers", 1)
+        elif type == "pattern":
+            if self.share_rep_net:
+                return self.g_rep_net
+            num_layers = kw.get("rep_num_pattern_layers", 1)
+        else:
+            raise ValueError(type)
+        if self.mem_len > 0 and num_layers > self.MAX_LAYERS:
+            raise ValueError("rep_net=TXL with %d %s layers: the reference keeps %d memories (one per entry of its rep-net "
+                             "container plus one) and layer i reads memory i, so more than %d layers fail"
+                             % (num_layers, type, self.MAX_LAYERS, self.MAX_LAYERS))
+        num_heads = self.num_heads
+        dropout = kw.get("rep_dropout", 0.0)
+        act_func = kw.get("rep_act_func", "relu")
+        pre_lnorm = kw.get("pre_lnorm", False)
+        txl = nn.ModuleList()
+        for i in range(num_layers):
+            txl.add_module("%s_txl_(%d)" % (type, i),
+                           _txl.TXLLayer(self.hid_dim, self.hid_dim, num_heads=num_heads, dropout=dropout, act_func=act_func,
+                                         pre_lnorm=pre_lnorm))
+        r_w_bias = nn.Parameter(th.Tensor(num_heads, self.hid_dim // num_heads))
+        r_r_bias = nn.Parameter(th.Tensor(num_heads, self.hid_dim // num_heads))
+        init_weight(r_w_bias, init="normal")
+        init_weight(r_r_bias, init="normal")
+        return _txl.RepNetDict({"txl": txl, "r_w_bias": r_w_bias, "r_r_bias": r_r_bias})
+
+    def memory_stays_empty(self):
+        """update_mems keeps ``cat(mem, hid)[:, beg:end]`` with ``end = mlen + max(0, qlen - ext_len)`` and qlen = seg_len."""
+        return self.mem_len <= 0 or self.ext_len >= self.seg_len
+
+    def _update_mems(self, hids, mems, mlen, qlen):
+        end = mlen + max(0, qlen - self.ext_len)
+        beg = max(0, end - self.mem_len)
+        new = []
+        for i, hid in enumerate(hids):
+            rows = hid if mlen == 0 else th.cat([mems[i], hid], dim=1)
+            new.append(rows[:, beg:end].detach())
+        return new
+
+    def _segment(self, x, x_mask, net, mems):
+        """One segment through every layer (txl.py:290-317): x [B, qlen, H], x_mask [B, qlen, 1] bool, mems a list of
+        [B, mlen, H] or None -> (output, the next segment's memories)."""
+        qlen = x.size(1)
+        mlen = mems[0].size(1) if mems is not None else 0
+        pos_seq = th.arange(mlen + qlen - 1, -1, -1, dtype=th.long, device=x.device)
+        if self.clamp_len > 0:
+            pos_seq = pos_seq.clamp(max=self.clamp_len)
+        outputs = [self.drop(x)]
+        r = self.drop(self.pos_emb(pos_seq).unsqueeze(0))
+        dead = ~x_mask
+        for i, layer in enumerate(net["txl"]):
+            m = None if mems is None else mems[i]
+            outputs.append(layer(outputs[-1], r, net["r_w_bias"], net["r_r_bias"], mems=m).masked_fill(dead, 0.0))
+        return outputs[-1], (None if mems is None else self._update_mems(outputs, mems, mlen, qlen))
+
+    def _rep(self, net, x, mask):
+        """x [B, L, H] (masked rows already zero), mask [B, L, 1] bool -> [B, L, H] (txl.py:350-358 with utils/dl.py:17-27)."""
+        B, L, H = x.shape
+        seg = self.seg_len
+        pad = (-L) % seg
+        if pad:                                  # the data is padded after its rows, the mask before them
+            x = th.cat([x, x.new_zeros((B, pad, H))], dim=1)
+            mask = th.cat([mask.new_zeros((B, pad, 1)), mask], dim=1)
+        S = (L + pad) // seg
+        if S > 1 and self.fold_segments and self.memory_stays_empty():
+            out, _ = self._segment(x.reshape(B * S, seg, H), mask.reshape(B * S, seg, 1), net, None)
+            return out.view(B, S * seg, H)[:, S * seg - L:]
+        mems = [x.new_empty((B, 0, H)) for _ in range(len(net) + 1)] if self.mem_len > 0 else None
+        outs = []
+        for s in range(S):
+            o, mems = self._segment(x[:, s * seg:(s + 1) * seg], mask[:, s * seg:(s + 1) * seg], net, mems)
+            outs.append(o)
+        return th.cat(outs, dim=1)[:, S * seg - L:]
+
+    def get_pattern_rep(self, p_emb, mask=None):
+        if mask is None:
+            mask = th.ones(p_emb.size()[:2] + (1,), dtype=th.bool, device=p_emb.device)
+        else:
+            p_emb = p_emb.masked_fill(~mask, 0.0)
+        return self._rep(self.p_rep_net, p_emb, mask)
+
+    def get_graph_rep(self, g_emb, mask=None, gate=None):
+        if mask is None:
+            mask = th.ones(g_emb.size()[:2] + (1,), dtype=th.bool, device=g_emb.device)
+        else:
+            g_emb = g_emb.masked_fill(~mask, 0.0)
+        if gate is not None:
+            g_emb = g_emb * gate
+        out = self._rep(self.g_rep_net, g_emb, mask)
+        return out if gate is None else out * gate
+
+
+SEQ_MODELS = {"CNN": CNN, "RNN": RNN, "TXL": TXL}

@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 93
+#define DMP_ABI_VERSION 94
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1528,6 +1528,27 @@ int dmp_relcorr_weights_fwd(const float *T, const float *loop_rel, const float *
  * sum_i T[b, (i + k) mod I] dWcat[i, b P + o];  dloop_rel [I] and dWloop [I, H]: the same for block R with loop_rel, Wloop. */
 int dmp_relcorr_weights_bwd(const float *dWcat, const float *T, const float *loop_rel, const float *Win, const float *Wloop, int R, int I,
                             int H, int P, float scale, float *dT, float *dloop_rel, float *dWin, float *dWloop, void *stream);
+
+/* ---- Transformer-XL relative-position attention of the TXL rep-net (dmp_txl.hip; SubgraphCountingMatching/models/txl.py:95-177,
+ * as `encoder_forward` runs it: no attention mask).  Per sequence n and head h, m = k - q:
+ *   BD[i, p] = (Q_i + r_r_bias) . R_p,   S[i, j] = scale ((Q_i + r_w_bias) . K_j + shift(BD)[i, j]),   O = softmax_j(S) V
+ * shift = the reference's rel_shift WITHOUT the causal mask that usually hides its wrap-around:
+ *   j - i < m + 1: BD[i, q - 1 - i + j];   j - i == m + 1: 0;   j - i > m + 1: BD[i + 1, j - i - m - 2] (the next row's query).
+ * Q [N, q, nh, dh], K / V [N, k, nh, dh], R [k, nh, dh], r_w_bias / r_r_bias [nh, dh], O [N, q, nh dh]: contiguous fp32, 16-byte
+ * aligned.  One workgroup per (sequence, head); no [N, q, k, nh] tensor in global memory.  fp32 fmaf chains, fixed order. */
+/* 1 for 1 <= q <= 64, q <= k <= 128 and dh in {16, 32, 64, 128}, else 0 (the entry points answer DMP_ERR_UNSUPPORTED). */
+int dmp_txl_supported(int q, int k, int dh);
+/* rowmax / rowsum [N, nh, q]: the maximum of every row of S and the sum of exp(S - max) (the backward's input). */
+int dmp_txl_attn_fwd(const float *Q, const float *K, const float *V, const float *R, const float *r_w_bias, const float *r_r_bias,
+                     int64_t N, int q, int k, int nh, int dh, float scale, float *O, float *rowmax, float *rowsum, void *stream);
+/* Number of partials of dmp_txl_attn_bwd (a function of the shapes only). */
+int64_t dmp_txl_bwd_groups(int64_t N, int nh);
+/* dQ (both paths summed) [N, q, nh, dh], dK / dV [N, k, nh, dh]; partial [dmp_txl_bwd_groups(N, nh), k + 2, nh, dh]: per group of
+ * sequences rows 0 .. k-1 dR, row k d r_w_bias, row k + 1 d r_r_bias; sum them with dmp_reduce_partials (L = (k + 2) nh dh).
+ * S is recomputed as the forward computed it.  No float atomics: bitwise reproducible. */
+int dmp_txl_attn_bwd(const float *Q, const float *K, const float *V, const float *R, const float *r_w_bias, const float *r_r_bias,
+                     const float *dO, const float *rowmax, const float *rowsum, int64_t N, int q, int k, int nh, int dh, float scale,
+                     float *dQ, float *dK, float *dV, float *partial, void *stream);
 
 #ifdef __cplusplus
 }
