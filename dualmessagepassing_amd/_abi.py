@@ -15,7 +15,7 @@ c_double = ctypes.c_double
 c_ptr = ctypes.c_void_p
 c_size = ctypes.c_size_t
 
-ABI_VERSION = 94
+ABI_VERSION = 95
 
 # ---- limits of the header that the host side relies on (``#define``s of the same names)
 DMP_COLLATE_MAX_JOBS = 4
@@ -233,6 +233,8 @@ SIGNATURES = {
     "dmp_smallk_atb_jobs": (c_int, [_p(dmp_smallk_job), c_int, c_int, c_int, c_ptr]),
     "dmp_l0_pack_jobs": (c_int, [_p(dmp_l0_pack_job), c_int, c_ptr]),
     "dmp_count_loss": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_f32, c_ptr, c_ptr, c_ptr]),
+    "dmp_match_loss_workspace_words": (c_i64, [c_i64, c_i64]),
+    "dmp_match_loss": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "dmp_reduce_partials_multi": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr]),
     "dmp_l0_pack": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr]),
     "dmp_l0_edge_fwd_masked": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,

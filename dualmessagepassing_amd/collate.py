@@ -128,11 +128,12 @@ def _offsets(sizes):
     return off
 
 
-def _pre_pad(flat, sizes, seg):
+def _pre_pad(flat, sizes, seg, max_len=None):
     """``batch_convert_tensor_to_tensor(rows, pre_pad=True)`` (utils/dl.py:89-110): row i of the
     result holds sample i's values right-aligned, zeros in front.  One host sync (the padded length,
-    as the reference's ``max(batch_lens)``)."""
-    B, m = int(sizes.numel()), int(sizes.max().item()) if sizes.numel() else 0
+    as the reference's ``max(batch_lens)``) unless ``max_len`` names it."""
+    B = int(sizes.numel())
+    m = int(max_len) if max_len is not None else (int(sizes.max().item()) if sizes.numel() else 0)
     out = torch.zeros((B, m), dtype=flat.dtype, device=flat.device)
     if flat.numel():
         off = _offsets(sizes)
@@ -151,8 +152,10 @@ def subiso_weights(pattern, graph, sub_flat, sample_ptr, return_weights=("node",
 
     pattern / graph: BatchedGraphs from ``collate_device`` / ``batch`` with ``edata["label"]``;
     sub_flat [T] int64: the samples' ``subisomorphisms`` tensors flattened back to back;
-    sample_ptr [B+1] int64: first element of each sample.  Returns ``(node_weights [B, max_nodes] |
-    None, edge_weights [B, max_edges] | None)``, int64."""
+    sample_ptr [B+1] int64: first element of each sample; ``sub_flat`` may be longer than ``sample_ptr[B]`` (padded to a
+    fixed capacity: the tail is ignored).  Returns ``(node_weights [B, max_nodes] | None, edge_weights [B, max_edges] |
+    None)``, int64; the padded lengths are the graph's ``max_num_nodes`` / ``max_num_edges`` where the collate recorded
+    them (what the model pads its rows to: no host sync then), else the largest size of the batch."""
     lib = _lib.load()
     if isinstance(return_weights, str):
         return_weights = return_weights.split(",")
@@ -175,7 +178,7 @@ def subiso_weights(pattern, graph, sub_flat, sample_ptr, return_weights=("node",
         flat = torch.empty(N, dtype=torch.int64, device=dev)
         check(lib.dmp_subiso_node_weights(ptr(sub_flat), T, ptr(sample_ptr), B, ptr(g_node_off), ptr(flat), N,
                                           ptr(status[0:]), st), "dmp_subiso_node_weights")
-        node_w = _pre_pad(flat, graph.batch_num_nodes(), _segment_ids(graph, "node"))
+        node_w = _pre_pad(flat, graph.batch_num_nodes(), _segment_ids(graph, "node"), getattr(graph, "max_num_nodes", None))
     if "edge" in return_weights:
         from .constants import EDGELABEL
         E, PE = graph.number_of_edges(), pattern.number_of_edges()
@@ -198,7 +201,7 @@ def subiso_weights(pattern, graph, sub_flat, sample_ptr, return_weights=("node",
                                           ptr(idx.out_ptr), ptr(idx.out_ent), ptr(idx.dst32),
                                           ptr(graph.edata[EDGELABEL].contiguous()), ptr(flat), E, int(work_hint),
                                           ptr(status[1:]), st), "dmp_subiso_edge_weights")
-        edge_w = _pre_pad(flat, graph.batch_num_edges(), _segment_ids(graph, "edge"))
+        edge_w = _pre_pad(flat, graph.batch_num_edges(), _segment_ids(graph, "edge"), getattr(graph, "max_num_edges", None))
     if validate and int(status.sum().item()) != 0:
         raise _lib.DmpError("subiso_weights: a subisomorphism row refers to a node outside its target graph")
     return node_w, edge_w

@@ -628,7 +628,8 @@ __device__ __forceinline__ int64_t upper_slot(const int64_t *ptr, int64_t n, int
 
 __global__ void subiso_node_k(const int64_t *sub, int64_t T, const int64_t *sample_ptr, int64_t B,
                               const int64_t *g_node_off, unsigned long long *out, int32_t *status) {
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < T; t += (int64_t)gridDim.x * blockDim.x) {
+  const int64_t used = sample_ptr[B] < T ? sample_ptr[B] : T;      // a `sub` padded to a capacity: the tail belongs to no sample
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < used; t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t i = upper_slot(sample_ptr, B, t);
     const int64_t v = sub[t], n = g_node_off[i + 1] - g_node_off[i];
     if (v < 0 || v >= n) { if (status) atomicOr(status, 1); continue; }

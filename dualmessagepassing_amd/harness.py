@@ -214,7 +214,17 @@ class PairDataset:
             out[key] = (max(2, max(int(x[key]["num_nodes"]) for x in self.samples)), max(1, max(len(x[key]["src"]) for x in self.samples)))
         return out
 
-    def batch_arrays(self, indices, device, pad=None):
+    def sub_capacity(self, batch_size):
+        """``subs`` for ``batch_arrays``: the summed length of the ``batch_size`` longest flattened ``subisomorphisms`` arrays
+        of the dataset -- what any batch of that many pairs fits.  One number per dataset and batch size."""
+        caps = self.__dict__.setdefault("_sub_caps", {})
+        key = (int(batch_size), len(self.samples))
+        if key not in caps:
+            lens = sorted((int(np.asarray(x["subisomorphisms"]).size) for x in self.samples), reverse=True)
+            caps[key] = int(sum(lens[:max(0, int(batch_size))]))
+        return caps[key]
+
+    def batch_arrays(self, indices, device, pad=None, subs=None):
         """The uploaded half of ``batchify``: ``(meta, tensors)`` with ``tensors`` = the pattern batch's nine arrays
         (local endpoints, sizes, ids, labels, reversed flags), the graph batch's nine and ``counts [B, 1]``, and ``meta``
         = per side ``(total nodes, total edges, largest graph's nodes, largest graph's edges)`` as host ints.  Everything
@@ -224,7 +234,11 @@ class PairDataset:
         ``weights [2 B, 1]``, is appended).  Pairs are
         independent in the model (block-diagonal batches, no BatchNorm), so the real pairs' predictions are unchanged and
         an inert pair, whose prediction carries no loss, adds exact zeros to every gradient: a ragged dataset then meets a
-        handful of batch shapes instead of one per batch."""
+        handful of batch shapes instead of one per batch.
+        ``subs`` (``sub_capacity``): two more tensors at the end, ``sub_flat [subs]`` int64 -- the pairs' ``subisomorphisms``
+        rows flattened back to back (one host concatenation, one upload), zeros from the real total on -- and ``sample_ptr
+        [pairs + 1]`` int64, the first element of every pair (an inert pair's range is empty; the last entry is the real
+        total): the inputs of ``collate.subiso_weights`` at a size that does not depend on the batch."""
         meta, tensors = [], []
         extra, level = 0, 0
         if pad is not None:
@@ -263,10 +277,22 @@ class PairDataset:
             else:
                 meta.append((int(nn_.sum()), int(ne_.sum()), int(nn_.max(initial=0)), int(ne_.max(initial=0))))
         counts = torch.tensor([self.samples[i]["counts"] for i in indices] + [0] * extra, dtype=torch.float32, device=device)
+        tail = []
+        if subs is not None:
+            rows = [np.asarray(self.samples[i]["subisomorphisms"], np.int64).reshape(-1) for i in indices]
+            ptr_host = np.zeros(len(indices) + extra + 1, np.int64)
+            np.cumsum([len(r) for r in rows], out=ptr_host[1:len(indices) + 1])
+            ptr_host[len(indices) + 1:] = ptr_host[len(indices)]
+            if ptr_host[-1] > int(subs):
+                raise ValueError("batch_arrays(subs=%d): the batch's subisomorphism rows take %d elements" % (int(subs), ptr_host[-1]))
+            flat = np.zeros(int(subs), np.int64)
+            if ptr_host[-1]:
+                flat[:ptr_host[-1]] = np.concatenate(rows)
+            tail = [torch.from_numpy(flat).to(device), torch.from_numpy(ptr_host).to(device)]
         if pad is None:
-            return tuple(meta), tensors + [counts.unsqueeze(-1)]
+            return tuple(meta), tensors + [counts.unsqueeze(-1)] + tail
         weights = torch.tensor([1.0] * len(indices) + [0.0] * extra, dtype=torch.float32, device=device)
-        return tuple(meta), tensors + [counts.unsqueeze(-1), weights.unsqueeze(-1)]
+        return tuple(meta), tensors + [counts.unsqueeze(-1), weights.unsqueeze(-1)] + tail
 
     @staticmethod
     def _inert_graphs(tot, cap_n, cap_e, extra, largest=None, vlabel=0, elabel=0):
@@ -544,6 +570,107 @@ def _match_terms(crit, pred, weights, mask, pred_c, neg_slp):
     return loss, reg
 
 
+def _coef3(coef, device, dtype):
+    """(neg_slope, match_loss_w, match_reg_w) as a tensor of three numbers on ``device``."""
+    if torch.is_tensor(coef):
+        return coef.reshape(-1)[:3].to(device=device, dtype=dtype)
+    return torch.tensor([float(c) for c in coef], dtype=dtype, device=device)
+
+
+def match_terms_tensor(pred, weights, mask, pred_c, coef, bp_loss, pair_weights=None):
+    """``match_terms`` in tensor ops, any dtype, no host sync (the CPU path, and the fp64 reference of the kernel's tests).
+    The definition (see ``match_terms``): real pairs = nonzero ``pair_weights``, n of them; window = the last Lr columns of
+    the real pairs, Lr the largest ``Lc - first live column`` among them; x = pred where mask else 0 -- a VALUE-only
+    replacement, as ``_match_terms``' in-place ``masked_fill_`` under ``no_grad``: the gradient still reaches ``pred`` at
+    a masked window position; sums over the window divided by n (0 for n == 0); exact zeros outside the window."""
+    B, Lc = pred.shape
+    dt, dev = pred.dtype, pred.device
+    c = _coef3(coef, dev, dt)
+    mask = mask.reshape(B, Lc) != 0
+    real = torch.ones(B, dtype=torch.bool, device=dev) if pair_weights is None else pair_weights.reshape(-1) != 0
+    n = real.sum().to(dt)
+    inv_n = torch.where(n > 0, 1.0 / n.clamp(min=1), torch.zeros_like(n))
+    cols = torch.arange(Lc, device=dev)
+    first = torch.where(mask, cols.view(1, -1), torch.full_like(cols, Lc).view(1, -1)).amin(dim=1) if Lc else cols.new_zeros(B)
+    ext = torch.where(real, Lc - first, torch.zeros_like(first))
+    Lr = ext.amax() if B else cols.new_zeros(())
+    window = real.view(-1, 1) & (cols.view(1, -1) >= Lc - Lr)
+    x = torch.where(mask, pred, pred - pred.detach())
+    t = torch.where(mask, weights.reshape(B, Lc).to(dt), torch.zeros((), dtype=dt, device=dev))
+    zero = torch.zeros_like(x)
+    crit = _CRIT[bp_loss]
+    act = torch.where(x > 0, x, x * c[0])
+    loss = torch.where(window, crit(act, t, reduction="none"), zero).sum() * inv_n
+    reg = torch.where(window, crit(F.relu(x - pred_c.reshape(B, 1)), zero, reduction="none"), zero).sum() * inv_n
+    return c[1] * loss + c[2] * reg, loss, reg
+
+
+class _MatchLossHIP(torch.autograd.Function):
+    """One matching term and the gradient seeds of its weighted sum in three launches (``dmp_match_loss``)."""
+
+    @staticmethod
+    def forward(ctx, pred, pred_c, weights, mask, coef, kind, pair_weights):
+        from . import _lib
+        from .attn import _out
+        lib = _lib.load()
+        B, Lc = pred.shape
+        p = pred.detach()
+        if p.stride(1) != 1 or p.stride(0) < Lc:
+            p = p.contiguous()
+        c = pred_c.detach().reshape(-1).contiguous()
+        w = weights.reshape(B, Lc).contiguous()
+        m = mask.reshape(B, Lc).contiguous()
+        m = m.view(torch.uint8) if m.dtype == torch.bool else (m != 0).view(torch.uint8)
+        pw = None if pair_weights is None else pair_weights.detach().reshape(-1).contiguous()
+        _lib.require_gpu(p, c, w, m, coef, pw)
+        words = int(lib.dmp_match_loss_workspace_words(B, Lc))
+        if words <= 0:
+            raise _lib.DmpError("dmp_match_loss: shape [%d, %d] is outside the kernel's range" % (B, Lc))
+        dev = p.device
+        ws = torch.empty(words, dtype=torch.int32, device=dev)
+        terms, dpred, dpred_c = _out((3,), torch.float32, dev), _out((B, Lc), torch.float32, dev), _out((B,), torch.float32, dev)
+        with _lib.timed("match_loss[B=%d,Lc=%d]", (B, Lc), 17 * B * Lc):
+            _lib.check(lib.dmp_match_loss(_lib.ptr(p), p.stride(0), _lib.ptr(w), _lib.ptr(m), _lib.ptr(c), _lib.ptr(pw), _lib.ptr(coef),
+                                          B, Lc, int(kind), _lib.ptr(terms), _lib.ptr(dpred), _lib.ptr(dpred_c), _lib.ptr(ws),
+                                          _lib.stream_ptr()), "dmp_match_loss")
+        ctx.dpred, ctx.dpred_c, ctx.c_shape = dpred, dpred_c, pred_c.shape
+        total, loss, reg = terms[2], terms[0], terms[1]
+        ctx.mark_non_differentiable(loss, reg)
+        return total, loss, reg
+
+    @staticmethod
+    def backward(ctx, g, _gl, _gr):
+        return ctx.dpred * g, (ctx.dpred_c * g).view(ctx.c_shape), None, None, None, None, None
+
+
+def match_terms(pred, weights, mask, pred_c, coef, bp_loss, pair_weights=None):
+    """The matching loss and regulariser of train.py:627-649 for one of pred_v / pred_e, aware of a padded batch:
+    ``(match_loss_w * loss + match_reg_w * reg, loss, reg)`` with
+
+        loss = (1/n) sum_window crit(leaky_relu(x, neg_slope) - t),     reg = (1/n) sum_window crit(relu(x - pred_c[i]))
+
+    ``pred`` [B, Lc], ``weights`` [B, Lc] (the pre-padded subisomorphism weights), ``mask`` [B, Lc], ``pred_c`` [B] or
+    [B, 1], ``coef`` = (neg_slope, match_loss_w, match_reg_w) as three numbers or a device tensor, ``pair_weights`` [B]
+    of 0 / 1 (0: an inert pair of a padded batch).  n = the real pairs; the window = the last Lr columns of the real
+    pairs, Lr the longest stretch from a real pair's first live column to the row's end; x / t = pred / weights where
+    ``mask``, else 0.  On an unpadded batch this is ``_match_terms`` (which stays the restatement it is checked against),
+    its treatment of masked positions included; a padded batch gives what its real pairs alone give.  Unlike
+    ``_match_terms`` it leaves ``pred`` as it is.  On the GPU in fp32 (int64 weights, a criterion of the kernel) it is one
+    autograd node over ``dmp_match_loss`` -- three launches, the coefficients read on the device, so a recorded step
+    replays with the values of its step --; anything else, and a shape the kernel refuses, goes through
+    ``match_terms_tensor``."""
+    B, Lc = pred.shape
+    if (bp_loss in _CRIT_KIND and pred.is_cuda and pred.dtype == torch.float32 and pred_c.dtype == torch.float32 and pred_c.is_cuda
+            and torch.is_tensor(weights) and weights.is_cuda and weights.dtype == torch.int64 and not weights.requires_grad
+            and mask.is_cuda and pred_c.numel() == B and weights.numel() == B * Lc and mask.numel() == B * Lc
+            and (pair_weights is None or (pair_weights.is_cuda and pair_weights.dtype == torch.float32 and pair_weights.numel() == B))):
+        from . import _lib
+        if int(_lib.load().dmp_match_loss_workspace_words(B, Lc)) > 0:       # 0: DMP_ERR_UNSUPPORTED for this shape
+            c = _coef3(coef, pred.device, torch.float32).contiguous()
+            return _MatchLossHIP.apply(pred, pred_c, weights, mask, c, _CRIT_KIND[bp_loss], pair_weights)
+    return match_terms_tensor(pred, weights, mask, pred_c, coef, bp_loss, pair_weights)
+
+
 def train_epoch(model, optimizer, dataset, batch_size, device, sync=None, bp_loss="MSE", eval_metric="MAE",
                 neg_slp=0.0, rep_reg_w=0.0, match_loss_w=0.0, match_reg_w=0.0, max_grad_norm=8.0, order=None,
                 schedule=None, epoch=0, match_weights=("node", "edge"), trace=None, graph=None):
@@ -553,7 +680,8 @@ def train_epoch(model, optimizer, dataset, batch_size, device, sync=None, bp_los
     coefficients and the learning rate follow the run configuration step by step, as train.py:499-600,686 do.  Returns
     ``{"bp_loss", "eval_metric"}`` (sample-weighted means, one host sync at the end).  ``trace``: a list that receives
     one ``(loss, eval_metric)`` pair of device scalars per step (what the reference writes to its SummaryWriter).
-    ``graph``: a ``GraphedTrainStep`` (see there) -- batches whose shape it has recorded are one HIP graph replay each."""
+    ``graph``: a ``GraphedTrainStep`` (see there) -- batches whose shape it has recorded are one HIP graph replay each;
+    steps with matching terms go to it when it was built with exactly those terms (``match_weights``), else they run here."""
     model.train()
     sync = sync or FlatGradSync(model)
     order = np.arange(len(dataset)) if order is None else np.asarray(order)
@@ -571,8 +699,11 @@ def train_epoch(model, optimizer, dataset, batch_size, device, sync=None, bp_los
             for group in optimizer.param_groups:
                 group["lr"] = schedule.lr()
         want = (tuple(match_weights) or None) if (match_loss_w > 0 or match_reg_w > 0) else None
-        if graph and want is None:
-            loss, ev = graph(dataset, idx, device, neg_slp, rep_reg_w)
+        # a recorded step computes the terms it was built with: it takes the batch when those are the wanted ones (with both
+        # coefficients 0 its matching terms are multiplied by 0 on the device: the same step, still one replay)
+        if graph and (want is None or set(want) == set(getattr(graph, "match_weights", ()))):
+            loss, ev = (graph(dataset, idx, device, neg_slp, rep_reg_w, match_loss_w, match_reg_w) if getattr(graph, "match_weights", ())
+                        else graph(dataset, idx, device, neg_slp, rep_reg_w))
             if schedule is not None:
                 schedule.sched_step += 1
             with torch.no_grad():
@@ -622,25 +753,33 @@ def train_epoch(model, optimizer, dataset, batch_size, device, sync=None, bp_los
 
 
 class GraphedTrainStep:
-    """The count-loss training step of ``train_epoch`` (collate, forward, loss, backward, gradient pack, clipping,
-    AdamW) as ONE HIP graph per batch shape (``dp.StepGraph``): at the reference's own batch size (64 pairs of small
+    """The training step of ``train_epoch`` (collate, forward, count loss and, with ``match_weights``, the subisomorphism
+    weights and the matching terms, backward, gradient pack, clipping, AdamW) as ONE HIP graph per batch shape (``dp.StepGraph``): at the reference's own batch size (64 pairs of small
     graphs, config.py) a step is ~150 launches of microseconds each behind ~3 ms of Python, and a replay is a single
     ``hipGraphLaunch``.  Needs one rank (no collective is recorded), ``FlatAdamW(capturable=True)`` and a dataset with
-    ``batch_arrays`` / ``graphs_from_arrays``.  The negative slope of the count loss and the representation
-    regulariser's weight are device scalars written before every replay, the learning rate goes through
+    ``batch_arrays`` / ``graphs_from_arrays``.  The negative slope of the losses, the representation regulariser's weight
+    and the two matching coefficients are device scalars written before every replay (a coefficient annealed to 0
+    multiplies its term by 0 on the device: the step keeps replaying), the learning rate goes through
     ``optimizer.sync_hyper()``.  Batches of a shape seen for the first time, and shapes beyond ``max_shapes``
     recordings, run eagerly -- through the same function, so both ways compute the same step.  Run the training loop
     under ``with step.steps.on_stream():`` when it also copies sizeable tensors between host and device (checkpoints,
     predictions): see ``dp.StepGraph`` (``fit(graph=True)`` does)."""
 
     def __init__(self, model, optimizer, sync, bp_loss="MSE", eval_metric="MAE", max_grad_norm=8.0, with_rep_reg=False,
-                 max_shapes=4, pad="auto"):
+                 max_shapes=4, pad="auto", match_weights=()):
         """``pad``: ragged datasets (every batch another pair of (N, E) totals: the reference's bucket-sorted batches,
         utils/sampler.py:10-84, train.py:1283-1290) never repeat a shape, so nothing would replay.  ``"auto"`` / True:
         batches are padded with inert pairs to one of ``max_shapes`` capacity levels (``PairDataset.batch_arrays(pad=...)``;
         "auto": only when the dataset's graphs differ in size); the inert pairs carry weight 0 in the loss and the metric.
         Not with the representation regulariser (it reads every row) or BatchNorm layers (their statistics would see the
-        inert rows): such runs keep the exact shapes."""
+        inert rows): such runs keep the exact shapes.
+        ``match_weights``: a tuple out of "node" and "edge" -- the step then takes the batch's subisomorphism rows at a
+        fixed capacity (``PairDataset.sub_capacity``: no new batch shape), computes the weights on the device
+        (``collate.subiso_weights``) and adds ``match_terms`` for every named term whose head the model has; the inert
+        pairs of a padded batch are left out of the terms by their pair weights.
+        ``hyper``, the step's last input, holds the four device scalars as (rep_reg_w, neg_slp, match_loss_w, match_reg_w):
+        in this order its last three are the contiguous coefficient triple ``dmp_match_loss`` reads.  Nothing outside this
+        class reads it."""
         from .dp import StepGraph
         from .seqmodel import EdgeSeqModel
         if isinstance(model, EdgeSeqModel):
@@ -652,6 +791,11 @@ class GraphedTrainStep:
             raise ValueError("GraphedTrainStep needs FlatAdamW(capturable=True)")
         self.model, self.optimizer, self.sync = model, optimizer, sync
         self.bp, self.ev, self.max_grad_norm, self.with_rep_reg = _CRIT[bp_loss], _CRIT[eval_metric], max_grad_norm, with_rep_reg
+        if isinstance(match_weights, str):
+            match_weights = match_weights.split(",")
+        self.match_weights = tuple(w for w in ("node", "edge") if w in (match_weights or ()))
+        self.bp_name = bp_loss
+        self._sub_caps = {}
         self.hyper = None
         self._hyper_host = None
         self.dataset_cls = None
@@ -664,8 +808,9 @@ class GraphedTrainStep:
     def _step(self, meta, *tensors):
         pattern, graph = self.dataset_cls.graphs_from_arrays(meta, tensors)
         n = 2 * self.dataset_cls.ARRAYS_PER_GRAPH
-        counts, hyper = tensors[n], tensors[-1]
-        weights = tensors[n + 1] if len(tensors) == n + 3 else None        # a padded batch: 1 for the real pairs, 0 for the inert ones
+        counts, hyper = tensors[n], tensors[-1]                 # hyper: (rep_reg_w, neg_slp, match_loss_w, match_reg_w)
+        subs = tensors[-3:-1] if self.match_weights else ()       # (sub_flat at the dataset's capacity, sample_ptr)
+        weights = tensors[n + 1] if len(tensors) == n + 3 + len(subs) else None        # a padded batch: 1 for the real pairs, 0 for the inert ones
         self.sync.detach_grads()
         lazy, self.model.lazy_edge_rep = getattr(self.model, "lazy_edge_rep", True), not self.with_rep_reg   # see train_epoch
         try:
@@ -673,7 +818,7 @@ class GraphedTrainStep:
         finally:
             self.model.lazy_edge_rep = lazy
         pred = out["pred_c"]
-        act = torch.where(pred > 0, pred, pred * hyper[0])                        # leaky_relu with the slope on the device
+        act = torch.where(pred > 0, pred, pred * hyper[1])                        # leaky_relu with the slope on the device
         if weights is not None:      # the mean over the REAL pairs (train.py:463-480's batch mean)
             loss = (self.bp(act, counts, reduction="none") * weights).sum() / weights.sum()
         else:
@@ -681,7 +826,18 @@ class GraphedTrainStep:
         if self.with_rep_reg:
             reg = sum(self.bp(out[k], torch.zeros_like(out[k])) * out[k].size(1)
                       for k in ("p_v_rep", "p_e_rep", "g_v_rep", "g_e_rep") if out[k] is not None)
-            loss = loss + hyper[1] * reg
+            loss = loss + hyper[0] * reg
+        if subs:
+            # the work of the edge-weight kernel (rows x pattern edges) sizes its grid only: a constant of the recording,
+            # from the capacity and the largest pattern
+            hint = int(subs[0].numel()) * max(1, int(meta[0][3])) // max(1, int(meta[0][2]))
+            with torch.no_grad():
+                node_w, edge_w = subiso_weights(pattern, graph, subs[0], subs[1], self.match_weights, validate=False, work_hint=hint)
+                if edge_w is not None:                         # train.py:636-641 (the graph models' is the identity)
+                    edge_w = self.model.refine_edge_weights(edge_w)
+            for w, pk, mk in ((node_w, "pred_v", "g_v_mask"), (edge_w, "pred_e", "g_e_mask")):
+                if w is not None and out[pk] is not None:
+                    loss = loss + match_terms(out[pk], w, out[mk], pred, hyper[1:4], self.bp_name, pair_weights=weights)[0]
         loss.backward()
         self.sync.pack()
         self.sync.sync()
@@ -700,55 +856,111 @@ class GraphedTrainStep:
             self._pad_spec = dataset.pad_buckets(len(indices), levels=self.max_shapes) if (self.pad is True or ragged) else False
         return self._pad_spec or None
 
-    def __call__(self, dataset, indices, device, neg_slp=0.0, rep_reg_w=0.0):
+    def __call__(self, dataset, indices, device, neg_slp=0.0, rep_reg_w=0.0, match_loss_w=0.0, match_reg_w=0.0):
         if rep_reg_w > 0 and not self.with_rep_reg:
             raise ValueError("GraphedTrainStep(with_rep_reg=True) to train with the representation regulariser")
+        if (match_loss_w > 0 or match_reg_w > 0) and not self.match_weights:
+            raise ValueError("GraphedTrainStep(match_weights=...) to train with the matching terms")
         self.dataset_cls = type(dataset)
         pad = self._padding(dataset, indices)
         if pad is not None and len(indices) > pad["batch"]:
             pad = None
-        meta, tensors = dataset.batch_arrays(indices, device, pad=pad) if pad is not None else dataset.batch_arrays(indices, device)
+        kw = {} if pad is None else {"pad": pad}
+        if self.match_weights:
+            size = pad["batch"] if pad is not None else len(indices)      # one capacity per batch size: what any such batch fits
+            if size not in self._sub_caps:
+                self._sub_caps[size] = dataset.sub_capacity(size)
+            kw["subs"] = self._sub_caps[size]
+        meta, tensors = dataset.batch_arrays(indices, device, **kw)
         if self.hyper is None:
-            self.hyper = torch.zeros(2, dtype=torch.float32, device=device)
-        if self._hyper_host != (float(neg_slp), float(rep_reg_w)):
-            self._hyper_host = (float(neg_slp), float(rep_reg_w))
-            self.hyper[0:1].fill_(float(neg_slp))
-            self.hyper[1:2].fill_(float(rep_reg_w))
+            self.hyper = torch.zeros(4, dtype=torch.float32, device=device)
+        host = (float(rep_reg_w), float(neg_slp), float(match_loss_w), float(match_reg_w))
+        if self._hyper_host != host:
+            for k, v in enumerate(host):
+                if self._hyper_host is None or self._hyper_host[k] != v:
+                    self.hyper[k:k + 1].fill_(v)
+            self._hyper_host = host
         return self.steps(meta, *tensors, self.hyper)
 
 
+def binary_auc(target, pred):
+    """``sklearn.metrics.roc_auc_score`` of two BINARY vectors (train.py:1014: ``counts > 0`` against ``relu(pred_c) > 0``):
+    a one-threshold ROC curve, whose area is (TPR + TNR) / 2.  NaN when ``target`` holds one class only (sklearn raises)."""
+    t, p = target.reshape(-1) != 0, pred.reshape(-1) != 0
+    pos, neg = int(t.sum()), int((~t).sum())
+    if pos == 0 or neg == 0:
+        return float("nan")
+    return 0.5 * (int((t & p).sum()) / pos + int((~t & ~p).sum()) / neg)
+
+
 @torch.no_grad()
-def evaluate_epoch(model, dataset, batch_size, device, eval_metric="MAE"):
-    """train.py:847-1061 reduced to the count metrics: MAE / MSE of ``relu(pred_c)`` and the
-    predictions themselves."""
+def evaluate_epoch(model, dataset, batch_size, device, eval_metric="MAE", match_weights=None):
+    """train.py:847-1061: MAE / MSE / RMSE of ``relu(pred_c)``, the AUC of ``relu(pred_c) > 0`` against ``counts > 0``
+    and the predictions themselves.  With ``match_weights`` ("node", "edge" or both; every sample needs its
+    ``subisomorphisms``) and a model whose heads return weights, also the matching half: per pair ``NED`` / ``EED`` = the
+    sum of ``|relu(pred) - weights|`` over the whole padded row (train.py:952,967 mask nothing there), their means
+    ``MNED`` / ``MEED``, and flat ``pred_v`` / ``pred_e`` / ``node_weights`` / ``edge_weights``: every pair's live
+    positions back to back."""
     model.eval()
     preds, targets = [], []
+    if isinstance(match_weights, str):
+        match_weights = match_weights.split(",")
+    want = tuple(w for w in ("node", "edge") if w in (match_weights or ()))
+    if want and not all(x.get("subisomorphisms") is not None for x in dataset.samples):
+        want = ()
+    match = {k: [] for k in ("NED", "EED", "pred_v", "pred_e", "node_weights", "edge_weights")}
     # no optimizer step here that could drop a batch which does not fit a gate capacity: every edge row as it stands
     cap, model.gate_capacity = getattr(model, "gate_capacity", None), None
     try:
         for i in range(0, len(dataset), batch_size):
             idx = np.arange(i, min(i + batch_size, len(dataset)))
-            pattern, graph, counts, _ = dataset.batchify(idx, device)
-            preds.append(F.relu(model(pattern, graph)["pred_c"]))
+            pattern, graph, counts, weights = dataset.batchify(idx, device, return_weights=want) if want else dataset.batchify(idx, device)
+            out = model(pattern, graph)
+            preds.append(F.relu(out["pred_c"]))
             targets.append(counts)
+            for w, pk, mk, ek, wk in ((weights[0], "pred_v", "g_v_mask", "NED", "node_weights"),
+                                      (weights[1], "pred_e", "g_e_mask", "EED", "edge_weights")):
+                if w is None or out[pk] is None:
+                    continue
+                w = (model.refine_node_weights if pk == "pred_v" else model.refine_edge_weights)(w.float())
+                live = out[mk].reshape(w.shape).bool()
+                match[wk].append(w[live])                     # row-major: pair after pair, each pair's live positions
+                match[pk].append(out[pk][live])
+                match[ek].append((F.relu(out[pk]) - w).abs().sum(dim=1))
     finally:
         model.gate_capacity = cap
     pred, target = torch.cat(preds), torch.cat(targets)
-    return {"MAE": float(F.l1_loss(pred, target)), "MSE": float(F.mse_loss(pred, target)),
-            "eval_metric": float(_CRIT[eval_metric](pred, target)), "pred": pred.view(-1).cpu(), "counts": target.view(-1).cpu()}
+    res = {"MAE": float(F.l1_loss(pred, target)), "MSE": float(F.mse_loss(pred, target)),
+           "eval_metric": float(_CRIT[eval_metric](pred, target)), "pred": pred.view(-1).cpu(), "counts": target.view(-1).cpu()}
+    res["RMSE"] = res["MSE"] ** 0.5
+    res["AUC"] = binary_auc(target > 0, pred > 0)
+    for k, parts in match.items():
+        if parts:
+            res[k] = torch.cat(parts).cpu()
+    for mean, k in (("MNED", "NED"), ("MEED", "EED")):
+        if k in res:
+            res[mean] = float(res[k].mean())
+    return res
 
 
-def evaluate_run(save_dir, datasets, device, batch_size=None, eval_metric=None, epoch=None, stamp=""):
+def evaluate_run(save_dir, datasets, device, batch_size=None, eval_metric=None, epoch=None, stamp="", match_weights=None):
     """``evaluate.py`` (lines 60-245) for a run directory written by ``fit`` (or by the reference's ``train.py``):
     ``config.json`` -> ``build_model``; the dev-best epoch of ``log.txt`` (``utils/log.py:60-76``) -> its ``epoch%d.pt``
     (strict load); every split of ``datasets`` (name -> PairDataset) evaluated and written to
     ``eval_<split>_results_<stamp>.json`` with the reference's result layout (``data`` / ``prediction`` / ``error``);
-    one "best" line per split appended to ``log.txt``.  Returns ``{split: {"MAE", "MSE", "eval_metric"}}``."""
+    one "best" line per split appended to ``log.txt``.  ``match_weights``: the run's own (``config.json``) unless given;
+    with it the result file also carries ``node_weights`` / ``edge_weights`` (``data``), ``pred_v`` / ``pred_e``
+    (``prediction``) and ``NED`` / ``EED`` / ``MNED`` / ``MEED`` (``error``) where the model and the split have them, and
+    always ``RMSE`` / ``AUC``.  Returns ``{split: {"MAE", "MSE", "eval_metric"}}``."""
     import json
     from . import dataio
     from .basemodel import build_model
     config = dataio.load_config(os.path.join(save_dir, "config.json"))
     metric = eval_metric or config.get("eval_metric", "MAE")
+    if match_weights is None:
+        match_weights = config.get("match_weights", None)
+    if isinstance(match_weights, str):
+        match_weights = [w for w in match_weights.split(",") if w in ("node", "edge")]
     if epoch is None:
         best = dataio.get_best_epochs(os.path.join(save_dir, "log.txt"))
         epoch = best["eval-" + metric]["dev"][0]
@@ -757,12 +969,19 @@ def evaluate_run(save_dir, datasets, device, batch_size=None, eval_metric=None, 
     out = {}
     with open(os.path.join(save_dir, "log.txt"), "a") as log:
         for split, ds in datasets.items():
-            res = evaluate_epoch(model, ds, batch_size or config.get("eval_batch_size", 64), device, eval_metric=metric)
+            res = evaluate_epoch(model, ds, batch_size or config.get("eval_batch_size", 64), device, eval_metric=metric,
+                                 match_weights=match_weights)
             out[split] = {k: res[k] for k in ("MAE", "MSE", "eval_metric")}
             ids = [x.get("id", str(i)) for i, x in enumerate(ds.samples)]
             with open(os.path.join(save_dir, "eval_%s_results_%s.json" % (split, stamp)), "w") as f:
-                json.dump({"data": {"id": ids, "counts": res["counts"].tolist()}, "prediction": {"pred_c": res["pred"].tolist()},
-                           "error": {"MAE": res["MAE"], "MSE": res["MSE"]}}, f)
+                doc = {"data": {"id": ids, "counts": res["counts"].tolist()}, "prediction": {"pred_c": res["pred"].tolist()},
+                       "error": {"MAE": res["MAE"], "MSE": res["MSE"], "RMSE": res["RMSE"], "AUC": res["AUC"]}}
+                for part, keys in (("data", ("node_weights", "edge_weights")), ("prediction", ("pred_v", "pred_e")),
+                                   ("error", ("NED", "EED", "MNED", "MEED"))):
+                    for k in keys:
+                        if k in res:
+                            doc[part][k] = res[k].tolist() if torch.is_tensor(res[k]) else res[k]
+                json.dump(doc, f)
             log.write(dataio.best_line(split, epoch, epoch, **{"eval-" + metric: "%.3f" % res["eval_metric"]}) + "\n")
     return out
 
@@ -821,9 +1040,14 @@ def fit(model, optimizer, train_set, dev_set, epochs, batch_size, device, save_d
         sched = train_kw.get("schedule")
         if sched is not None:
             reg = sched.config.get("rep_reg_w", 0.0)
-        with_reg = (isinstance(reg, str) and reg.strip() not in ("", "0", "0.0")) or (not isinstance(reg, str) and float(reg) > 0)
+        on = lambda v: (isinstance(v, str) and v.strip() not in ("", "0", "0.0")) or (not isinstance(v, str) and float(v) > 0)
+        with_reg = on(reg)
+        # the matching terms likewise: recorded when one of their coefficients can be non-zero at any step
+        coefs = [(sched.config if sched is not None else train_kw).get(k, 0.0) for k in ("match_loss_w", "match_reg_w")]
+        match = train_kw.get("match_weights", ("node", "edge")) if any(on(c) for c in coefs) else ()
         train_kw["graph"] = GraphedTrainStep(model, optimizer, sync, bp_loss=train_kw.get("bp_loss", "MSE"), eval_metric=eval_metric,
-                                             max_grad_norm=train_kw.get("max_grad_norm", 8.0), with_rep_reg=with_reg) if ok else None
+                                             max_grad_norm=train_kw.get("max_grad_norm", 8.0), with_rep_reg=with_reg,
+                                             match_weights=match) if ok else None
     elif not train_kw.get("graph"):
         train_kw.pop("graph", None)
     rng = np.random.default_rng(seed)

@@ -209,7 +209,7 @@ class PredictNet(nn.Module):
         h = self.hidden_dim
         W, b = self.weight_fc1.weight, self.weight_fc1.bias
         Wp, Wg, Wd, Wm, Ws = W[:, :h], W[:, h:2 * h], W[:, 2 * h:3 * h], W[:, 3 * h:4 * h], W[:, 4 * h:]
-        ps = sizes[:, (0, 2)]                                  # (pl, 1/pl)
+        ps = th.stack([sizes[:, 0], sizes[:, 2]], dim=1)       # (pl, 1/pl); (indexing by a host tuple uploads it: not capturable)
         per_pair = th.addmm(b, p, (Wp - Wd).t()) + ps @ Ws.t()                       # [B, h]
         hidden = self.act(g_rows @ (Wg + Wd).t() + (g_rows * p.unsqueeze(1)) @ Wm.t() + per_pair.unsqueeze(1))
         W2, b2 = self.weight_fc2.weight, self.weight_fc2.bias

@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 94
+#define DMP_ABI_VERSION 95
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -215,6 +215,7 @@ int dmp_dedupe_first(const int64_t *key_a, const int64_t *key_l,
  *   sample_ptr  : [B+1] first element of each sample in `sub`.
  *   *_node_off / *_edge_off : [B+1] offsets of the batched pattern (p) / target (g) graph.
  *   dmp_subiso_node_weights : out[g_node_off[i] + x] = #rows of sample i containing x.
+ *                 Elements at or after sample_ptr[B] are ignored (a `sub` padded to a fixed capacity).
  *   dmp_pattern_edge_active : active[j] = 1 iff pattern edge j lies in the LAST run of equal
  *                 consecutive (src, dst) pairs of its graph (the reference's per-key dict keeps
  *                 only that run, dataset.py:79-88).
@@ -1020,6 +1021,27 @@ int dmp_heads_forward(const dmp_head_weights *w, const dmp_head_io *io, int num_
 int dmp_count_loss(const float *pred, const float *target, int64_t n, int kind, float neg_slope, float *loss, float *dpred, void *stream);
 int dmp_heads_backward(const dmp_head_weights *w, const dmp_head_io *io, const dmp_head_grads *g,
                        int num_heads, int B, int H, float slope, void *stream);
+
+/* One matching term of a training step (train.py:627-649, node or edge) AND the gradient seeds of its weighted sum, aware of
+ * a padded batch's capacity:
+ *   pred [B, Lc] fp32 (row stride ldp >= Lc), w [B, Lc] int64 (the pre-padded subisomorphism weights), mask [B, Lc] uint8,
+ *   pred_c [B], pair_w [B] (0 / 1; NULL: every pair counts; 0 = an inert pair of a padded batch),
+ *   coef: DEVICE pointer to (neg_slope, match_loss_w, match_reg_w) -- read by the kernels, so a replayed recording sees the
+ *   values of its step.  kind 0 MSE, 1 MAE, 2 smooth L1 (beta 1), as dmp_count_loss.
+ * With n = #real pairs, ext_i = Lc - (first live column of row i) (0 without one), Lr = max ext_i over the real pairs, the
+ * window = the last Lr columns of the real pairs, x = mask ? pred : 0, t = mask ? float(w) : 0:
+ *   terms[0] = loss = (1/n) sum_window crit(leaky_relu(x, neg_slope) - t)
+ *   terms[1] = reg  = (1/n) sum_window crit(relu(x - pred_c[i]))
+ *   terms[2] = match_loss_w * loss + match_reg_w * reg,   dpred [B, Lc] / dpred_c [B] = its gradient
+ * as the reference's in-place masked_fill_ under no_grad leaves it: a masked position INSIDE the window passes
+ * match_reg_w * crit'(relu(-pred_c[i])) * [0 > pred_c[i]] / n to pred; outside the window every gradient is exactly 0.
+ * n == 0: every output 0.  Every element of terms, dpred and dpred_c is written.  Three launches per call, no atomics, fixed
+ * summation order (bit-stable).  workspace: dmp_match_loss_workspace_words(B, Lc) 32-bit words; dpred 16-byte aligned.
+ * DMP_ERR_UNSUPPORTED (the caller uses its tensor ops; 0 words): B or Lc 0, B * Lc >= 2^31, Lc > 2^30. */
+int64_t dmp_match_loss_workspace_words(int64_t B, int64_t Lc);
+int dmp_match_loss(const float *pred, int64_t ldp, const int64_t *w, const uint8_t *mask, const float *pred_c,
+                   const float *pair_w, const float *coef, int64_t B, int64_t Lc, int kind, float *terms, float *dpred,
+                   float *dpred_c, void *workspace, void *stream);
 
 /*
  * Blend of the heads' counts by the sizes of their target graphs (basemodel.py:1488-1494):
