@@ -15,7 +15,7 @@ c_double = ctypes.c_double
 c_ptr = ctypes.c_void_p
 c_size = ctypes.c_size_t
 
-ABI_VERSION = 95
+ABI_VERSION = 96
 
 # ---- limits of the header that the host side relies on (``#define``s of the same names)
 DMP_COLLATE_MAX_JOBS = 4
@@ -29,6 +29,9 @@ DMP_GEMM_MAX_JOBS = 12
 DMP_GEMM_MAX_TERMS = 3
 DMP_ATB_MAX_JOBS = 8
 DMP_MEM_MEAN, DMP_MEM_SUM, DMP_MEM_MAX = 0, 1, 2      # the pooling modes of dmp_mem_init_fwd / _bwd
+DMP_LRP_MAX_NEIGHBOURS = 32                            # distinct out-neighbours of a node the permutation index admits
+DMP_LRP_MAX_SEQ_LEN = 6
+DMP_LRP_OVER_CAP, DMP_LRP_SELF_LOOP, DMP_LRP_DROPPED = 1, 2, 4      # bits of the status word of dmp_lrp_count / _fill
 
 
 # ---- the structs, named and ordered as in the header; pointers are c_void_p (assigned from ``data_ptr()`` / None)
@@ -376,4 +379,7 @@ SIGNATURES = {
     "dmp_txl_bwd_groups": (c_i64, [c_i64, c_int]),
     "dmp_txl_attn_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_f32,
                                  c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "dmp_lrp_workspace_words": (c_size, [c_i64, c_i64]),
+    "dmp_lrp_count": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "dmp_lrp_fill": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
 }

@@ -201,6 +201,13 @@ class PairDataset:
             self._edge_seq = EdgeSeqPairs(self)
         return self._edge_seq
 
+    def lrp(self, seq_len=4):
+        """The local-relational-pooling view of this dataset (``LRPPairs``): what the LRP / DMPLRP models train on."""
+        views = self.__dict__.setdefault("_lrp_views", {})
+        if int(seq_len) not in views:
+            views[int(seq_len)] = LRPPairs(self, seq_len)
+        return views[int(seq_len)]
+
     ARRAYS_PER_GRAPH = 9    # src, dst, num_nodes, num_edges, node id, node label, edge id, edge label, is_reversed
 
     def pad_buckets(self, batch_size, levels=4):
@@ -324,6 +331,81 @@ class PairDataset:
                              ndata={"id": nid, "label": vlabel}, edata={"id": eid, "label": elabel, "is_reversed": rev},
                              max_nodes=max_n, max_edges=max_e))
         return collate_device_many(jobs)                         # both sides in one pair of launches
+
+
+class LRPPairs(PairDataset):
+    """A ``PairDataset`` as the LRP / DMPLRP models need it (the part of the reference's ``LRPDataset``, dataset.py:1642-1862,
+    that is not the enumeration itself): once, here on the host, every sample's number of ego-net permutations per side and
+    the largest number of distinct neighbours, from the degree sequences alone (``PermIndex.counts_host``: closed form), and
+    the check that no graph has a non-reversed self-loop.  The batches it hands out are ``PairDataset``'s, with the hints on
+    the graph objects (``lrp_seq_len``, ``lrp_max_degree`` and ``lrp_total`` or ``lrp_capacity``) that let
+    ``model(pattern, graph)`` build both permutation indexes on the device without reading anything back.
+    ``batch_arrays(perms=perm_capacity(...))``: the indexes are built at a capacity level instead of their exact totals --
+    what a recorded step needs; the level is part of ``meta`` (the step's shape signature)."""
+
+    def __init__(self, pairs, seq_len=4):
+        from .lrp import PermIndex
+        self.samples, self.shape, self.seq_len = pairs.samples, pairs.shape, int(seq_len)
+        self.perm_counts = np.zeros((len(self.samples), 2), np.int64)          # [sample, (pattern, graph)]
+        self.max_degree = 0
+        for i, x in enumerate(self.samples):
+            for side, key in enumerate(("pattern", "graph")):
+                g = x[key]
+                total, deg, loop = PermIndex.counts_host(g["src"], g["dst"], g["num_nodes"], g.get("rev"), self.seq_len)
+                if loop:
+                    raise ValueError("sample %d (%s): %s has a non-reversed self-loop, which a permutation index cannot hold"
+                                     % (i, x.get("id", "?"), key))
+                self.perm_counts[i, side] = total
+                self.max_degree = max(self.max_degree, deg)
+
+    def lrp(self, seq_len=4):
+        return self if int(seq_len) == self.seq_len else PairDataset(self.samples, self.shape).lrp(seq_len)
+
+    def subset(self, indices):
+        return PairDataset.subset(self, indices).lrp(self.seq_len)
+
+    def model_config(self, hid_dim=64, layers=3, rep_net="DMPLRP", **kw):
+        kw.setdefault("lrp_seq_len", self.seq_len)
+        return PairDataset.model_config(self, hid_dim, layers, rep_net, **kw)
+
+    def perm_capacity(self, batch_size, levels=4):
+        """``perms`` for ``batch_arrays``: per level k = 1 .. ``levels`` the ``(pattern, graph)`` capacities in permutations,
+        k / levels of the sum of the ``batch_size`` largest counts of the dataset per side (as ``pad_buckets`` /
+        ``sub_capacity`` lay their levels out).  The top level holds any batch of that many pairs."""
+        top = [int(np.sort(self.perm_counts[:, side])[::-1][:max(0, int(batch_size))].sum()) for side in (0, 1)]
+        return tuple(tuple(-(-t * k // int(levels)) for t in top) for k in range(1, int(levels) + 1))
+
+    def batch_arrays(self, indices, device, pad=None, subs=None, perms=None):
+        """``PairDataset.batch_arrays`` with one more entry at the end of ``meta``: ``("lrp", seq_len, max_degree, level,
+        pattern total, graph total, pattern capacity, graph capacity)`` -- the exact totals (``perms`` None: an eager step) or
+        the capacities at a level of ``perms`` (``perm_capacity``): the smallest level that holds the target side, the top
+        level for the pattern side.  With ``pad`` the inert pairs count too: an inert graph is a ring, each of its nodes
+        has one neighbour at most and so exactly one permutation, whatever ``seq_len``; a capacity then grows by the padded
+        batch's node total (a constant of the padding level)."""
+        meta, tensors = PairDataset.batch_arrays(self, indices, device, pad=pad, subs=subs)
+        idx = np.asarray(indices, np.int64)
+        totals = [int(t) for t in self.perm_counts[idx].sum(axis=0)] if len(idx) else [0, 0]
+        if pad is not None:
+            for side, key in enumerate(("pattern", "graph")):
+                totals[side] += int(meta[side][0]) - sum(int(self.samples[i][key]["num_nodes"]) for i in indices)
+        hint = ("lrp", self.seq_len, max(self.max_degree, 1 if pad is not None else 0))
+        if perms is None:
+            return meta + (hint + (0,) + tuple(totals) + (None, None),), tensors
+        grow = [int(meta[side][0]) if pad is not None else 0 for side in (0, 1)]
+        # the level is the target side's (where the permutations are: ~100 x the patterns' at the README sizes); the pattern
+        # side always takes its top level -- a joint level let a few hundred pattern permutations push the target side up
+        level = next((k for k, caps in enumerate(perms, 1) if totals[1] <= caps[1] + grow[1]), None)
+        if level is None or totals[0] > perms[-1][0] + grow[0]:
+            raise ValueError("batch_arrays(perms=...): the batch's %d / %d permutations exceed the top capacity level" % tuple(totals))
+        return meta + (hint + (level, None, None, perms[-1][0] + grow[0], perms[level - 1][1] + grow[1]),), tensors
+
+    @classmethod
+    def graphs_from_arrays(cls, meta, tensors):
+        _, seq_len, max_degree, _level, p_total, g_total, p_cap, g_cap = meta[-1]
+        pattern, graph = super().graphs_from_arrays(meta[:-1], tensors)
+        for g, total, cap in ((pattern, p_total, p_cap), (graph, g_total, g_cap)):
+            g.lrp_seq_len, g.lrp_max_degree, g.lrp_total, g.lrp_capacity = seq_len, max_degree, total, cap
+        return pattern, graph
 
 
 class EdgeSeqPairs:
@@ -796,6 +878,7 @@ class GraphedTrainStep:
         self.match_weights = tuple(w for w in ("node", "edge") if w in (match_weights or ()))
         self.bp_name = bp_loss
         self._sub_caps = {}
+        self._perm_caps = {}
         self.hyper = None
         self._hyper_host = None
         self.dataset_cls = None
@@ -862,10 +945,20 @@ class GraphedTrainStep:
         if (match_loss_w > 0 or match_reg_w > 0) and not self.match_weights:
             raise ValueError("GraphedTrainStep(match_weights=...) to train with the matching terms")
         self.dataset_cls = type(dataset)
+        lrp = hasattr(dataset, "perm_capacity")          # the LRP view: both permutation indexes at a capacity level
         pad = self._padding(dataset, indices)
         if pad is not None and len(indices) > pad["batch"]:
             pad = None
         kw = {} if pad is None else {"pad": pad}
+        if lrp:
+            from . import _abi
+            if dataset.max_degree > _abi.DMP_LRP_MAX_NEIGHBOURS or not 1 <= dataset.seq_len <= _abi.DMP_LRP_MAX_SEQ_LEN:
+                raise ValueError("GraphedTrainStep: a node with %d distinct neighbours / lrp_seq_len %d is outside the device "
+                                 "index build (the host build cannot be recorded): train eagerly" % (dataset.max_degree, dataset.seq_len))
+            size = pad["batch"] if pad is not None else len(indices)
+            if size not in self._perm_caps:
+                self._perm_caps[size] = dataset.perm_capacity(size, levels=self.max_shapes)
+            kw["perms"] = self._perm_caps[size]
         if self.match_weights:
             size = pad["batch"] if pad is not None else len(indices)      # one capacity per batch size: what any such batch fits
             if size not in self._sub_caps:

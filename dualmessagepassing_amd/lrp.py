@@ -16,18 +16,21 @@ the pooling matrix averages a CONTIGUOUS range of permutations per node (dataset
     node = scale[:, None] * seg_pool(out, ranges)                  the segment-sum kernel over contiguous ranges
 
 ``PermIndex`` holds the slot vector / ranges / scales of a batch; it is built from the reference's three sparse
-tensors (``from_sparse``: what ``LRPDataset.batchify`` hands over) or from the ego-net permutations directly.
+tensors (``from_sparse``: what ``LRPDataset.batchify`` hands over), from the ego-net permutations enumerated on the host
+(``from_graphs``) or from the batched graph itself on the device (``from_batched``: csrc/dmp_lrp.hip, count -> scan -> fill).
+``model(pattern, graph)`` builds both sides' indexes with ``from_batched``: the call form of the training loop.
 """
 from itertools import permutations
 
 import numpy as np
 import torch as th
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
-from . import _lib, ops
+from . import _abi, _lib, ops
 from .act import init_module, init_weight, map_activation_str_to_layer
 from .basemodel import GraphAdjModelV2
-from .constants import INDEGREE
+from .constants import INDEGREE, REVFLAG
 from .dmpnn import DMPLayer
 from .graph import as_batched
 
@@ -44,6 +47,9 @@ class PermIndex:
         self.num_nodes, self.num_edges, self.seq_len = int(num_nodes), int(num_edges), int(seq_len)
         self.num_perms = int(slot.numel()) // (seq_len * seq_len)
         self._pool = None
+        self._csr = None
+        self.status = None      # from_batched: int64 [1] on the device, the OR of the DMP_LRP_* bits
+        self.live = None        # an index padded to a capacity: float [num_perms], 1 for the real permutations, 0 for the tail
 
     @classmethod
     def from_sparse(cls, pooling_matrix, node_to_perm, edge_to_perm, seq_len=4):
@@ -104,6 +110,134 @@ class PermIndex:
             else th.ones(sizes.numel(), device=device)
         return cls(slot, sizes, scale, total_n, total_e, seq_len)
 
+    @staticmethod
+    def counts_host(src, dst, num_nodes, is_reversed=None, seq_len=4):
+        """``(permutations, largest number of distinct neighbours, has a non-reversed self-loop)`` of ONE graph from its degree
+        sequence alone: a node with n distinct non-reversed out-neighbours has n! / (n - k)! permutations, k = min(L - 1, n)
+        (host arrays; no enumeration)."""
+        src, dst, n = np.asarray(src, np.int64), np.asarray(dst, np.int64), int(num_nodes)
+        if is_reversed is not None:
+            keep = ~np.asarray(is_reversed, bool)
+            src, dst = src[keep], dst[keep]
+        deg = np.bincount(np.unique(src * max(n, 1) + dst) // max(n, 1), minlength=n) if len(src) else np.zeros(n, np.int64)
+        total = 0
+        for d, many in zip(*np.unique(deg, return_counts=True)):
+            f = 1
+            for i in range(min(seq_len - 1, int(d))):
+                f *= int(d) - i
+            total += f * int(many)
+        return total, int(deg.max(initial=0)), bool((src == dst).any())
+
+    @classmethod
+    def from_batched(cls, graph, seq_len=4, pooling="mean", total=None, capacity=None):
+        """From the batched graph itself, on the device (``dmp_lrp_count`` -> ``dmp_exclusive_scan_i64`` -> ``dmp_lrp_fill``):
+        the index ``from_graphs`` builds for the batch's single graphs, memoised on the graph object per ``seq_len``.
+        ``total``: the number of permutations where the caller knows it (a dataset does: ``counts_host``), else ONE read from
+        the device sizes the output.  ``capacity`` (in permutations): the index then holds exactly ``capacity`` permutations
+        -- the tail reads the zero row, is pooled by no node and is masked out of ``perm_pool`` (``live``) -- the total is
+        never read back, and surplus permutations are dropped with ``DMP_LRP_DROPPED`` in ``status``: the form a recorded
+        step needs.  A graph object that carries ``lrp_max_degree`` (the dataset's validation: largest number of distinct
+        neighbours, no self-loop) is not asked for its status word; any other costs one read of it.  A non-reversed
+        self-loop is a ``ValueError``; a node above ``DMP_LRP_MAX_NEIGHBOURS``, a ``seq_len`` outside the kernels' range or
+        a graph that is not on the GPU goes through ``from_graphs`` on the batch split into its graphs: the same result."""
+        g = as_batched(graph)
+        L = int(seq_len)
+        if L < 1:
+            raise ValueError("lrp_seq_len must be positive")
+        ix = g.index() if g._src.is_cuda else None
+        memo = g.__dict__.setdefault("_lrp_index", {})
+        key = (L, pooling, None if capacity is None else int(capacity))
+        hit = memo.get(key)
+        if hit is not None and hit[0] is ix:
+            _lib.pin_for_capture(hit[1].slot, hit[1].sizes, hit[1].scale, hit[1].live)
+            return hit[1]
+        N, E = g.number_of_nodes(), g.number_of_edges()
+        known = getattr(g, "lrp_max_degree", None)
+        admitted = (ix is not None and 1 <= L <= _abi.DMP_LRP_MAX_SEQ_LEN and N + E + 1 < (1 << 31)
+                    and (known is None or known <= _abi.DMP_LRP_MAX_NEIGHBOURS))
+        perm = cls._build_device(g, ix, L, pooling, total, capacity, known is None) if admitted else None
+        if perm is None:
+            perm = cls._build_host(g, L, pooling, capacity)
+        if not (g._src.is_cuda and th.cuda.is_current_stream_capturing()):     # arrays made inside a recording live in its pool
+            memo[key] = (ix, perm)
+        return perm
+
+    @classmethod
+    def _build_device(cls, g, ix, L, pooling, total, capacity, read_status):
+        """The kernels' index, or None when the status word names a node above the neighbour cap."""
+        lib = _lib.load()
+        N, E, dev = g.number_of_nodes(), g.number_of_edges(), g.device
+        i64 = dict(dtype=th.int64, device=dev)
+        sizes, scale = th.empty(N, **i64), th.empty(N, dtype=th.float32, device=dev)
+        off = th.empty(N + 2, **i64)                       # [N + 1] offsets (off[N]: the total), then the status word
+        status = off[N + 1:]
+        ws = th.empty(int(lib.dmp_lrp_workspace_words(N, E)), dtype=th.int32, device=dev)
+        scan_ws = th.empty(int(lib.dmp_scan_workspace_words(N)), **i64)
+        st = _lib.stream_ptr()
+        _lib.check(lib.dmp_lrp_count(_lib.ptr(ix.out_ptr), _lib.ptr(ix.out_ent), _lib.ptr(ix.dst32), N, E, L, int(pooling == "mean"),
+                                     _lib.ptr(ws), _lib.ptr(sizes), _lib.ptr(scale), _lib.ptr(status), st), "dmp_lrp_count")
+        _lib.check(lib.dmp_exclusive_scan_i64(_lib.ptr(sizes), N, _lib.ptr(off), _lib.ptr(scan_ws), st), "dmp_exclusive_scan_i64")
+        if read_status or (total is None and capacity is None):
+            real, bits = (int(x) for x in off[N:].tolist())             # the one read: total and status side by side
+            if bits & _abi.DMP_LRP_SELF_LOOP:
+                raise ValueError("PermIndex.from_batched: a non-reversed self-loop (slot (i, i) cannot hold a node and an edge)")
+            if bits & _abi.DMP_LRP_OVER_CAP:
+                return None
+            if total is not None and int(total) != real:
+                raise ValueError("PermIndex.from_batched: total=%d but the graph has %d permutations" % (int(total), real))
+            total = real
+        P = int(total) if capacity is None else int(capacity)
+        slot = th.empty(P * L * L, **i64)
+        _lib.check(lib.dmp_lrp_fill(_lib.ptr(ix.out_ptr), _lib.ptr(ws), _lib.ptr(off), N, E, L, P, _lib.ptr(slot), _lib.ptr(status), st),
+                   "dmp_lrp_fill")
+        perm = cls(slot, sizes, scale, N, E, L)
+        perm.status = status
+        if capacity is not None:
+            perm.live = (th.arange(P, device=dev) < off[N:N + 1]).float()
+        return perm
+
+    @classmethod
+    def _build_host(cls, g, L, pooling, capacity):
+        """``from_graphs`` on the batch split back into its graphs (host speed), padded or cut to ``capacity``."""
+        src, dst = g._src.cpu().numpy(), g._dst.cpu().numpy()
+        rev = g.edata[REVFLAG].cpu().numpy().astype(bool) if REVFLAG in g.edata else None
+        bnn, bne = g.batch_num_nodes().cpu().tolist(), g.batch_num_edges().cpu().tolist()
+        graphs, n0, e0 = [], 0, 0
+        for n, e in zip(bnn, bne):
+            s, d = src[e0:e0 + e] - n0, dst[e0:e0 + e] - n0
+            r = None if rev is None else rev[e0:e0 + e]
+            if bool(((s == d) & (True if r is None else ~r)).any()):
+                raise ValueError("PermIndex.from_batched: a non-reversed self-loop (slot (i, i) cannot hold a node and an edge)")
+            graphs.append((s, d, n, r))
+            n0, e0 = n0 + n, e0 + e
+        perm = cls.from_graphs(graphs, g.device, L, pooling)
+        perm.status = th.zeros(1, dtype=th.int64, device=g.device)
+        if capacity is not None:
+            P, real, L2 = int(capacity), perm.num_perms, L * L
+            slot = th.full((P * L2,), perm.num_nodes + perm.num_edges, dtype=th.int64, device=g.device)
+            slot[:min(P, real) * L2] = perm.slot[:min(P, real) * L2]
+            if real > P:
+                perm.status += _abi.DMP_LRP_DROPPED
+            perm.slot, perm.num_perms = slot, P
+            perm.live = (th.arange(P, device=g.device) < real).float()
+        return perm
+
+    def slot_csr(self):
+        """``(slot32, rowptr, ent)``: the slots as int32 (the gather's index) and the CSR of the slots by table row over the
+        node and edge rows only -- the zero row fills most slots of a batch and its gradient is nobody's: a slot that reads
+        it is outside ``[0, N + E)`` for ``dmp_csr_build``, which leaves such entries out (one row of several 10^5 entries
+        would otherwise be sorted and summed by a single thread)."""
+        if self._csr is None:
+            lib = _lib.load()
+            M, R, dev = int(self.slot.numel()), self.num_nodes + self.num_edges, self.slot.device
+            i32 = dict(dtype=th.int32, device=dev)
+            rowptr, ent, status = th.empty(R + 1, **i32), th.empty(M, **i32), th.empty(1, **i32)
+            ws = th.empty(int(lib.dmp_csr_workspace_words(R, M)), **i32)
+            _lib.check(lib.dmp_csr_build(_lib.ptr(self.slot), None, M, R, _lib.ptr(rowptr), _lib.ptr(ent), None, None, _lib.ptr(status),
+                                         _lib.ptr(ws), _lib.stream_ptr()), "dmp_csr_build(slots)")
+            self._csr = (self.slot.to(th.int32), rowptr, ent)
+        return self._csr
+
     def pool_index(self):
         if self._pool is None:
             self._pool = ops.PoolIndex(self.sizes, num_rows=self.num_perms)
@@ -125,18 +259,40 @@ def as_perm_index(graph, pooling_matrix, node_to_perm, edge_to_perm, seq_len):
     return cached[2]
 
 
+class _SlotRows(th.autograd.Function):
+    """Rows of ``[node_feat ; edge_feat ; 0]`` at the slots of a ``PermIndex``: forward one row gather, backward the
+    fixed-order segment sum over ``PermIndex.slot_csr`` straight into the two gradients."""
+
+    @staticmethod
+    def forward(ctx, node_feat, edge_feat, perm):
+        _lib.require_gpu(node_feat, edge_feat, perm.slot)
+        slot32, ctx.rowptr, ctx.ent = perm.slot_csr()
+        ctx.N, ctx.E = perm.num_nodes, perm.num_edges
+        table = th.cat([node_feat, edge_feat, node_feat.new_zeros((1, node_feat.size(1)))], dim=0)
+        return ops.gather_rows_raw(table, slot32)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g = ops.seg_sum_raw(d.contiguous(), ctx.rowptr, ctx.ent, ctx.N + ctx.E, rows_shared=False)
+        return g[:ctx.N], g[ctx.N:], None
+
+
 def perm_pool(perm, node_feat, edge_feat, weight, bias=None, act=None):
     """``pooling @ act(einsum(slots(node_feat, edge_feat), weight) + bias)`` (lrp.py:66-73 / dmplrp.py:188-194 with
     ``act`` None): gather, one dense product over the L*L slots, per-node segment sum, scale."""
     L2 = perm.seq_len * perm.seq_len
-    table = th.cat([node_feat, edge_feat, node_feat.new_zeros((1, node_feat.size(1)))], dim=0)
-    rows = ops.take_rows(table, perm.slot)                                        # [P * L*L, in]
+    if node_feat.size(0) != perm.num_nodes or edge_feat.size(0) != perm.num_edges:
+        raise ValueError("perm_pool: the permutation index was built for %d nodes / %d edges" % (perm.num_nodes, perm.num_edges))
+    rows = _SlotRows.apply(node_feat, edge_feat, perm)                            # [P * L*L, in]
     w = weight.permute(2, 0, 1).reshape(L2 * weight.size(0), weight.size(1))      # [(slot, in), hid]
     out = ops.matmul_xw(rows.view(perm.num_perms, L2 * weight.size(0)), w)
     if bias is not None:
         out = out + bias
     if act is not None:
         out = act(out)
+    if perm.live is not None:          # the tail of an index at a capacity: exact zeros forward and backward
+        out = out * perm.live.view(-1, 1)
     return ops.seg_pool(out, perm.pool_index()) * perm.scale.view(-1, 1)
 
 
@@ -286,14 +442,32 @@ class _PermRepMixin:
         return self._run(self.g_rep_net, graph, v, e, (g_perm_pool, g_n_perm_matrix, g_e_perm_matrix), v_gate=v_gate, e_gate=e_gate)
 
 
+def _is_graph(obj):
+    return hasattr(obj, "all_edges") and hasattr(obj, "number_of_nodes")
+
+
 class _PermModel(_PermRepMixin, GraphAdjModelV2):
     """The 8-argument forward of lrp.py:222-390 / dmplrp.py:332-470 on the common skeleton: the permutation inputs ride
-    along on the graph objects while ``GraphAdjModelV2.forward`` runs."""
+    along on the graph objects while ``GraphAdjModelV2.forward`` runs.  ``model(pattern, graph)`` -- the call form of the
+    training loop -- builds (or reuses) both sides' indexes on the device (``PermIndex.from_batched``), with the host hints
+    a dataset leaves on the graphs (``lrp_total`` / ``lrp_capacity``, valid for ``lrp_seq_len``)."""
 
     edge_head_skips_reversed = False      # lrp.py:240-243 / dmplrp.py:350-353: plain length masks
 
-    def forward(self, pattern, p_perm_pool, p_n_perm_matrix, p_e_perm_matrix, graph, g_perm_pool=None, g_n_perm_matrix=None,
-                g_e_perm_matrix=None):
+    def _seq_len(self):
+        return next(iter(self.g_rep_net[self.rep_key])).lrp_seq_len
+
+    def _own_index(self, graph):
+        L = self._seq_len()
+        hinted = getattr(graph, "lrp_seq_len", None) == L
+        return PermIndex.from_batched(graph, L, total=getattr(graph, "lrp_total", None) if hinted else None,
+                                      capacity=getattr(graph, "lrp_capacity", None) if hinted else None)
+
+    def forward(self, pattern, p_perm_pool, p_n_perm_matrix=None, p_e_perm_matrix=None, graph=None, g_perm_pool=None,
+                g_n_perm_matrix=None, g_e_perm_matrix=None):
+        if graph is None and p_n_perm_matrix is None and _is_graph(p_perm_pool):      # model(pattern, graph)
+            pattern, graph = as_batched(pattern), as_batched(p_perm_pool)
+            p_perm_pool, g_perm_pool = self._own_index(pattern), self._own_index(graph)
         pattern, graph = as_batched(pattern), as_batched(graph)
         self._perm = {id(pattern): (p_perm_pool, p_n_perm_matrix, p_e_perm_matrix), id(graph): (g_perm_pool, g_n_perm_matrix, g_e_perm_matrix)}
         try:

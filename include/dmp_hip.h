@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 95
+#define DMP_ABI_VERSION 96
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1571,6 +1571,34 @@ int64_t dmp_txl_bwd_groups(int64_t N, int nh);
 int dmp_txl_attn_bwd(const float *Q, const float *K, const float *V, const float *R, const float *r_w_bias, const float *r_r_bias,
                      const float *dO, const float *rowmax, const float *rowsum, int64_t N, int q, int k, int nh, int dh, float scale,
                      float *dQ, float *dK, float *dV, float *partial, void *stream);
+
+/* ---- The ego-net permutation index of local relational pooling (dmp_lrp.hip; SubgraphCountingMatching/dataset.py:1751-1797 +
+ * :1817-1860, what LRPDataset enumerates per sample on the host) for a whole batched graph, from its CSR by source
+ * (out_ptr / out_ent / dst32 of dmp_csr_build_pair; an entry's flag bit is the edge's is_reversed).  Per node v:
+ *   nbrs(v)    the distinct destinations of v's non-reversed out-edges, ascending;  edge(a, b) = the LAST non-reversed edge a -> b
+ *   perms(v)   (v,) + q for q over the k-permutations of nbrs(v) in lexicographic order of positions, k = min(L - 1, |nbrs|):
+ *              sizes[v] = |nbrs|! / (|nbrs| - k)! of them (1 for a node without neighbours), scale[v] = 1 / sizes[v] (mean) or 1
+ *   slots      every permutation owns L L consecutive int64: (i, i) = perm[i], (i, j) = N + edge(perm[i], perm[j]) where that
+ *              edge exists, N + E everywhere else (rows / columns past the permutation's length included)
+ * Permutations are laid out node after node.  Three steps: dmp_lrp_count, dmp_exclusive_scan_i64 of sizes [N] into off [N + 1]
+ * (off[N] = the total), dmp_lrp_fill.  Admitted: 1 <= L <= DMP_LRP_MAX_SEQ_LEN and N + E + 1 < 2^31 (else
+ * DMP_ERR_UNSUPPORTED); a node with more than DMP_LRP_MAX_NEIGHBOURS distinct neighbours gets sizes[v] = 0 and sets
+ * DMP_LRP_OVER_CAP.  Integer results, no float atomics, the status word is only OR-ed into: bitwise reproducible.
+ *   ws      dmp_lrp_workspace_words(N, E) int32 words, written by count and read by fill
+ *   status  [1] int64: cleared by dmp_lrp_count, then the OR of DMP_LRP_OVER_CAP, DMP_LRP_SELF_LOOP (a non-reversed self-loop:
+ *           slot (i, i) would have to hold a node and an edge) and, from dmp_lrp_fill, DMP_LRP_DROPPED
+ *   fill    writes exactly capacity L L slots: the permutations [0, min(total, capacity)), then N + E; it reads the total on
+ *           the device only.  total > capacity: the surplus permutations are dropped and DMP_LRP_DROPPED is set. */
+#define DMP_LRP_MAX_NEIGHBOURS 32
+#define DMP_LRP_MAX_SEQ_LEN 6
+#define DMP_LRP_OVER_CAP 1
+#define DMP_LRP_SELF_LOOP 2
+#define DMP_LRP_DROPPED 4
+size_t dmp_lrp_workspace_words(int64_t N, int64_t E);
+int dmp_lrp_count(const int32_t *out_ptr, const int32_t *out_ent, const int32_t *dst32, int64_t N, int64_t E, int L, int mean,
+                  int32_t *ws, int64_t *sizes, float *scale, int64_t *status, void *stream);
+int dmp_lrp_fill(const int32_t *out_ptr, const int32_t *ws, const int64_t *off, int64_t N, int64_t E, int L, int64_t capacity,
+                 int64_t *slot, int64_t *status, void *stream);
 
 #ifdef __cplusplus
 }

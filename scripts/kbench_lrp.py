@@ -1,0 +1,145 @@
+"""The permutation index of LRP / DMPLRP and a DMPLRP training step on the GPU, at batch 64 of the ragged set in the size
+ranges of the reference's README "Complex" setting (``harness.SmallLikePairs``: patterns <= 8 / 8, graphs <= 64 / 256, reversed
+edges added), hid 64, lrp_seq_len 4.
+
+    python scripts/kbench_lrp.py                 # index: from_graphs against from_batched; step: eager against replayed
+    python scripts/kbench_lrp.py --out FILE      # ... and the result line written to FILE as well
+
+Index: both sides of the same batches, ``PermIndex.from_graphs`` (a host loop and one upload: wall clock around a
+synchronise) against ``PermIndex.from_batched`` on fresh graph objects whose CSR index is already built, with the
+dataset's hints (no read back): device events around ``--iters`` builds, median over the batches.  The two are compared
+entry by entry first.
+Step: ``train_epoch`` over the same batches, eager (exact totals) and through ``GraphedTrainStep`` (padded batches,
+capacity levels), each on its own copy of the model, warmed first, alternating windows; device events around windows
+that end in a synchronise.  Peak memory: the rise of ``torch.cuda.max_memory_allocated`` over a way's warm-up (for the
+replayed way that is where the recordings' memory pools are allocated), above what was allocated before it."""
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch as th
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def window(fn, steps):
+    a, b = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
+    th.cuda.synchronize()
+    a.record()
+    fn()
+    b.record()
+    th.cuda.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def host_side(view, idx, key):
+    return [(view.samples[i][key]["src"], view.samples[i][key]["dst"], view.samples[i][key]["num_nodes"], view.samples[i][key]["rev"]) for i in idx]
+
+
+def bench_index(a, view, dev):
+    from dualmessagepassing_amd.lrp import PermIndex
+    L, B = view.seq_len, a.batch
+    host_ms, dev_ms, perms = [], [], []
+    for i in range(0, a.batches * B, B):
+        idx = np.arange(i, i + B)
+        th.cuda.synchronize()
+        t0 = time.perf_counter()
+        ref = [PermIndex.from_graphs(host_side(view, idx, key), dev, L) for key in ("pattern", "graph")]
+        th.cuda.synchronize()
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+        meta, tensors = view.batch_arrays(idx, dev)
+        graphs = view.graphs_from_arrays(meta, tensors)
+        for g, r in zip(graphs, ref):
+            got = PermIndex.from_batched(g, L, total=g.lrp_total)
+            assert th.equal(got.slot, r.slot) and th.equal(got.sizes, r.sizes) and th.equal(got.scale, r.scale)
+            g.__dict__.pop("_lrp_index")
+
+        def build():
+            for _ in range(a.iters):
+                for g in graphs:
+                    PermIndex.from_batched(g, L, total=g.lrp_total)
+                    g.__dict__.pop("_lrp_index")            # the memo: every build is a real one
+        build()
+        dev_ms.append(window(build, a.iters))
+        perms.append(sum(r.num_perms for r in ref))
+    return {"batches": a.batches, "permutations_per_batch_median": float(np.median(perms)), "from_graphs_ms_median": float(np.median(host_ms)),
+            "from_graphs_ms_min": min(host_ms), "from_graphs_ms_max": max(host_ms), "from_batched_ms_median": float(np.median(dev_ms)),
+            "from_batched_ms_min": min(dev_ms), "from_batched_ms_max": max(dev_ms),
+            "speedup_median": float(np.median(host_ms) / np.median(dev_ms))}
+
+
+def bench_step(a, view, dev):
+    from dualmessagepassing_amd.basemodel import build_model
+    from dualmessagepassing_amd.dp import FlatAdamW, FlatGradSync
+    from dualmessagepassing_amd.harness import GraphedTrainStep, train_epoch
+    B = a.batch
+    ds = view.subset(range(a.batches * B))
+    th.manual_seed(0)
+    base = build_model(**ds.model_config(hid_dim=64, layers=3))
+    runs = {}
+    for way in ("eager", "replay"):
+        model = copy.deepcopy(base).to(dev)
+        sync = FlatGradSync(model)
+        opt = FlatAdamW([sync.flatten_parameters()], lr=1e-4, weight_decay=1e-5, amsgrad=True, capturable=True)
+        step = GraphedTrainStep(model, opt, sync, max_shapes=4) if way == "replay" else None
+        runs[way] = (lambda model=model, opt=opt, sync=sync, step=step: train_epoch(model, opt, ds, B, dev, sync=sync, neg_slp=0.01, graph=step), step)
+    times, peak = {way: [] for way in runs}, {}
+    replay = runs["replay"][1]
+    ctx = replay.steps.on_stream()
+    ctx.__enter__()
+    try:
+        for way, (fn, _) in runs.items():                   # warm-up: first launches, the recordings -- and the peak: a
+            th.cuda.synchronize()                           # recording's pool is allocated here and only reused later
+            before = th.cuda.memory_allocated()
+            th.cuda.reset_peak_memory_stats()
+            for _ in range(a.warmup):
+                fn()
+            th.cuda.synchronize()
+            peak[way] = (th.cuda.max_memory_allocated() - before) / 2 ** 20
+        for _ in range(a.windows):
+            for way, (fn, _) in runs.items():
+                times[way].append(window(fn, a.batches))
+    finally:
+        ctx.__exit__(None, None, None)
+    res = {"batches_per_window": a.batches, "windows": a.windows}
+    for way, ts in times.items():
+        res[way] = {"ms_per_step_median": float(np.median(ts)), "ms_per_step_min": min(ts), "ms_per_step_max": max(ts),
+                    "steps": len(ts) * a.batches, "peak_memory_above_start_mib": peak[way]}
+    res["replay"]["replays"], res["replay"]["eager_calls"] = replay.steps.replays, replay.steps.eager_calls
+    res["speedup"] = res["eager"]["ms_per_step_median"] / res["replay"]["ms_per_step_median"]
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--batches", type=int, default=8, help="batches of the set (steps per window)")
+    ap.add_argument("--iters", type=int, default=20, help="timed device index builds per batch")
+    ap.add_argument("--windows", type=int, default=20, help="timed windows per way of the step")
+    ap.add_argument("--warmup", type=int, default=3, help="warm-up windows per way")
+    ap.add_argument("--seq_len", type=int, default=4)
+    ap.add_argument("--skip_step", action="store_true")
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    from dualmessagepassing_amd.harness import SmallLikePairs
+    dev = th.device("cuda:0")
+    view = SmallLikePairs(a.batch * a.batches, seed=1).lrp(a.seq_len)
+    res = {"batch": a.batch, "lrp_seq_len": a.seq_len, "hid_dim": 64, "max_distinct_degree": view.max_degree,
+           "index": bench_index(a, view, dev)}
+    if not a.skip_step:
+        res["step"] = bench_step(a, view, dev)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
