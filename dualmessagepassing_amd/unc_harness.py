@@ -236,3 +236,43 @@ def graph_of(triplets_np, num_nodes, num_rels, device):
     """``(graph, triplets on the device)`` for ``train_unsupervised`` from ``load_links``' output."""
     trip = np.asarray(triplets_np)[:, :3]
     return build_graph_from_triplets(num_nodes, num_rels, trip, device), torch.from_numpy(trip).to(device)
+
+
+def split_links(triplets, test_fraction, seed):
+    """A seeded hold-out split of the links: ``(train, test)``, ``test`` a random ``round(test_fraction * M)`` rows (at
+    least one, at most M - 1), both in the original order.  The permutation is drawn on the CPU: the same split on every
+    device."""
+    if not 0.0 < test_fraction < 1.0:
+        raise ValueError("test_fraction lies strictly between 0 and 1, got %r" % (test_fraction,))
+    M = triplets.size(0)
+    if M < 2:
+        raise ValueError("a split needs at least two links")
+    n_test = min(M - 1, max(1, int(round(test_fraction * M))))
+    perm = torch.randperm(M, generator=torch.Generator().manual_seed(seed))
+    held = torch.zeros(M, dtype=torch.bool)
+    held[perm[:n_test]] = True
+    held = held.to(triplets.device)
+    return triplets[~held], triplets[held]
+
+
+@torch.no_grad()
+def evaluate_links(model, graph, train_triplets, test_triplets, known=None, filtered=True, ks=(1, 3, 10), ties="mean", **sampling):
+    """Rank the held-out ``test_triplets`` with the model's own decoder: ``collect_node_embeddings`` over the training
+    graph (``sampling``: its keyword arguments), then ``unc_eval.link_ranks`` / ``link_metrics`` with ``model.w_relation``,
+    both sides.  ``filtered``: every other known true entity of a query leaves its candidates -- ``known`` [M, 3], by
+    default training + test links.  For every encoder ``unc.TrainModel`` builds and for ``unc_compgcn.TrainModel``.
+    -> the metrics dict (one host sync besides the sampling's)."""
+    from . import unc_eval
+    w_relation = getattr(model, "w_relation", None)
+    if w_relation is None:
+        raise ValueError("this model has no w_relation: it was built with nlabel > 0 (a node classifier), and the link "
+                         "ranking needs the DistMult decoder of nlabel == 0")
+    train_triplets = train_triplets[:, :3].to(torch.int64)
+    test_triplets = test_triplets[:, :3].to(device=train_triplets.device, dtype=torch.int64)
+    was_training = model.training
+    node_emb, _ = collect_node_embeddings(model, graph, train_triplets, **sampling)
+    model.train(was_training)
+    if filtered and known is None:
+        known = torch.cat([train_triplets, test_triplets])
+    ranks = unc_eval.link_ranks(w_relation, node_emb, test_triplets, known=known if filtered else None, ties=ties)
+    return unc_eval.link_metrics(ranks, ks=ks)

@@ -43,7 +43,7 @@ extern "C" {
 #define DMP_ERR_HIP (-3)         /* a HIP launch failed; see dmp_last_hip_error()   */
 
 /* ABI version of this header; bumped on any signature change. */
-#define DMP_ABI_VERSION 96
+#define DMP_ABI_VERSION 97
 int dmp_abi_version(void);
 /* hipGetLastError() text of the most recent DMP_ERR_HIP on this host thread. */
 const char *dmp_last_hip_error(void);
@@ -1599,6 +1599,22 @@ int dmp_lrp_count(const int32_t *out_ptr, const int32_t *out_ent, const int32_t 
                   int32_t *ws, int64_t *sizes, float *scale, int64_t *status, void *stream);
 int dmp_lrp_fill(const int32_t *out_ptr, const int32_t *ws, const int64_t *off, int64_t N, int64_t E, int L, int64_t capacity,
                  int64_t *slot, int64_t *status, void *stream);
+
+/* ---- Rank counts of a link predictor's decoder (dmp_rank.hip; the ranking evaluation a DistMult trainer carries -- the
+ * reference's UNC drivers dropped it, UnsupervisedNodeClassification/Model/DMPNN/src/main.py:185-211 only writes the embeddings).
+ *   score(i, c) = sum_h query[i, h] table[c, h],   t_i = score(i, target[i])
+ *   greater[i] = #{c in C_i : score(i, c) > t_i},  equal[i] = #{c in C_i : score(i, c) == t_i}
+ *   C_i = {c in [0, N) : c != target[i] and c not in filt_idx[filt_ptr[i] .. filt_ptr[i + 1])}     (by index, never by value)
+ * query [Q, H], table [N, H]: contiguous fp32.  target [Q] with 0 <= target < N (a value outside is clamped for the gather).
+ * filt_ptr [Q + 1] / filt_idx [nnz]: CSR of excluded candidates, ascending inside a row, may hold the target, may be empty;
+ * both NULL: no filter.  Every score is one k-ascending fp32 fmaf chain (the f32-input MFMA), t_i included, so a candidate whose
+ * table row equals the target's row counts in `equal`; a NaN score counts in neither.  The [Q, N] scores are never stored and
+ * nothing is allocated: greater / equal [Q] are zeroed on the stream, then added to with integer atomics (order-independent,
+ * bitwise repeatable).  Admitted: dmp_rank_supported(H) and N < 2^31 - 256, Q < 2^31 - 128 (else DMP_ERR_UNSUPPORTED). */
+/* 1 for 1 <= H <= 256, else 0; no launch. */
+int dmp_rank_supported(int H);
+int dmp_rank_counts(const float *query, const float *table, const int64_t *target, const int64_t *filt_ptr, const int64_t *filt_idx,
+                    int64_t nnz, int64_t Q, int64_t N, int H, int32_t *greater, int32_t *equal, void *stream);
 
 #ifdef __cplusplus
 }
