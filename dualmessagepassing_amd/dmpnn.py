@@ -299,6 +299,19 @@ def _union_of(pattern, graph):
     return u[1]
 
 
+def _joint_index(union, H=None):
+    """``(index, coef)`` of the union graph: its CSR index and its degree coefficients (each made once per graph) and, at a width
+    ``H`` the MFMA kernels take, the per-edge selectors."""
+    from . import fused
+    ix = union.index()
+    if OUTDEGREE not in union.ndata:
+        union.ndata[OUTDEGREE] = union.out_degrees()
+    coef = ix.degree_coef(union.ndata[OUTDEGREE])
+    if H is not None and fused.mfma_ok(ix, H):
+        ix.edge_select(coef)
+    return ix, coef
+
+
 def prepare_joint(pattern, graph, hidden_dim=128, backward=True, class_tiles=True):
     """Everything of the joint pattern + target pass that depends on the batch's STRUCTURE only -- the union graph, its
     CSR index, degrees, coefficient vector, per-edge selectors, degree-class tiles and (``backward``) the incidence CSR --
@@ -311,12 +324,7 @@ def prepare_joint(pattern, graph, hidden_dim=128, backward=True, class_tiles=Tru
     if (REVFLAG in pattern.edata) != (REVFLAG in graph.edata):
         return None
     union = _union_of(pattern, graph)
-    ix = union.index()
-    if OUTDEGREE not in union.ndata:
-        union.ndata[OUTDEGREE] = union.out_degrees()
-    coef = ix.degree_coef(union.ndata[OUTDEGREE])
-    if fused.mfma_ok(ix, hidden_dim):
-        ix.edge_select(coef)
+    ix, coef = _joint_index(union, hidden_dim)
     if class_tiles and fused.typed_ok(ix, hidden_dim):
         ix.class_tiles(coef)
     if backward and not (ops.USE_GRAPH_SEG_SUM and ix.node_tiling is not None and hidden_dim in (64, 128)):
@@ -388,13 +396,7 @@ def prefetch_joint_indexes(model, pattern, graph, v_gate, e_gate, pool_kinds=(),
         with side.fork() as forked:
             if not forked:
                 return
-            union = _union_of(pattern, graph)
-            ix = union.index()
-            if OUTDEGREE not in union.ndata:
-                union.ndata[OUTDEGREE] = union.out_degrees()
-            coef = ix.degree_coef(union.ndata[OUTDEGREE])
-            if fused.mfma_ok(ix, H):
-                ix.edge_select(coef)
+            ix, coef = _joint_index(_union_of(pattern, graph), H)
             side.mark("index")
             side.mark("nodes")
             side.mark("erows")
@@ -409,35 +411,24 @@ def prefetch_joint_indexes(model, pattern, graph, v_gate, e_gate, pool_kinds=(),
     with side.fork() as forked:
         if not forked:
             return
-        union = _union_of(pattern, graph)
-        ix = union.index()
-        if OUTDEGREE not in union.ndata:
-            union.ndata[OUTDEGREE] = union.out_degrees()
-        coef = ix.degree_coef(union.ndata[OUTDEGREE])
-        if fused.mfma_ok(ix, H):
-            ix.edge_select(coef)
+        ix, coef = _joint_index(_union_of(pattern, graph), H)
         side.mark("index")
         vg, eg = _joint_gates(v_gate, e_gate, np_, ep_, th.float32, e_gate.device)
-        N, E = ix.num_nodes, ix.num_edges
-        typed = fused.typed_ok(ix, H)
-        # both gates' row masks, the three kept-row lists below and the kept nodes' selectors: three launches instead of ten
-        # (fused.gate_bundle plants each product in the memo its own function reads; the conditions are those tested below)
-        want_nodes = bool(N >= 4096 and fused.onepanel_ok(H) and fused.USE_NODE_ROWS and fused.USE_PLAIN_ATB and fused.zero_rows_gate(vg) and typed and E > 0)
-        want_l0 = bool(typed and fused.SKIP_DEAD_ROWS and fused.USE_ROW_MASKS and fused.USE_L0_ROW_LISTS and len(layers) > 1 and ep_ % 32 == 0
-                       and E - ep_ >= fused.L0_LIST_MIN_ROWS and th.is_grad_enabled())
-        want_asc = bool(typed and fused.zero_rows_gate(eg) and fused.USE_PLAIN_ATB and gatememo.flag(eg, "binary"))
-        fused.gate_bundle(ix, vg, eg, want_nodes, (ep_, E) if want_l0 else None, want_asc)
-        nd = None
-        if N >= 4096 and fused.onepanel_ok(H):
-            nd = fused.node_rows(ix, vg, H)
+        E, grad = ix.num_edges, th.is_grad_enabled()
+        dead_h1, dead_e = fused.dead_h1_rows(ix, H, eg), fused.dead_edge_rows(ix, H, eg)
+        want_nodes = fused.kept_node_path(ix, H, vg)
+        want_l0 = dead_h1 and fused.l0_row_list(ep_, E - ep_) and len(layers) > 1 and grad
+        # both gates' row masks, the three kept-row lists below and the kept nodes' selectors in three launches instead of ten, each
+        # planted in the memo its own function reads (fused.gate_bundle)
+        fused.gate_bundle(ix, vg, eg, want_nodes, (ep_, E) if want_l0 else None, dead_e and fused.USE_PLAIN_ATB)
+        nd = fused.node_rows(ix, vg, H) if want_nodes else None
         side.mark("nodes")
-        if typed and fused.SKIP_DEAD_ROWS and fused.USE_ROW_MASKS:
+        if dead_h1:
             mask = fused.gate_row_mask(eg)
-            if (mask is not None and fused.USE_L0_ROW_LISTS and len(layers) > 1 and ep_ % 32 == 0 and E - ep_ >= fused.L0_LIST_MIN_ROWS
-                    and th.is_grad_enabled()):
+            if want_l0:
                 fused.kept_rows(mask, ep_, E)          # the first layer's target rows (fused.l0_edge_fwd / l0_bwd_w)
         side.mark("erows")
-        if typed and fused.zero_rows_gate(eg):
+        if dead_e:
             fused.live_tiles(ix, coef, eg)
             fused.ascending_tiles(eg)                  # the plain-panel launches' row order
             side.mark("tiles")
@@ -446,13 +437,12 @@ def prefetch_joint_indexes(model, pattern, graph, v_gate, e_gate, pool_kinds=(),
         if pool_kinds:
             from .basemodel import _pool_indexes_union
             built = dict(zip(pool_kinds, _pool_indexes_union(pattern, graph, pool_kinds, skip_rev)))
-            if built.get("edge") is not None and typed and fused.zero_rows_gate(eg) and th.is_grad_enabled():
+            if built.get("edge") is not None and dead_e and grad:
                 fused.keep_pool_csr(built["edge"], eg)     # the pooled passes of the last layer over the kept edges
                 if getattr(built["edge"], "rows_in_order", False):
                     fused.pool_weight_sums(built["edge"], eg)     # ... and the gate's per-graph sums (the pooled second Linear's bias term)
         side.mark("pools")
-        if (nd is not None and typed and fused.USE_MASKED_SUMS and fused.zero_rows_gate(eg) and H % 4 == 0
-                and fused.gate_row_mask(eg) is not None and th.is_grad_enabled()):
+        if fused.kept_incidence_sums(ix, H, eg, nd is not None) and grad:
             nd.kept_incidence(ix, eg)
         side.mark("incidence")
 
@@ -463,8 +453,7 @@ def joint_rep(model, pattern, graph, p_v_emb, p_e_emb, g_v_emb, g_e_emb, v_gate=
     every layer is eligible for the fused path.  Pattern rows get gate 1 (the pattern side has no
     gate, basemodel.py:1515).  Returns ``(p_v_rep, p_e_rep, g_v_rep, g_e_rep)`` or ``None`` if not
     applicable (callers then run the two loops separately)."""
-    from . import fused
-    from .collate import union_graphs
+    from . import fused, side
     if not getattr(model, "use_fused", True) or model.p_rep_net is not model.g_rep_net:
         return None
     layers = list(model.g_rep_net[model.rep_key])
@@ -478,23 +467,19 @@ def joint_rep(model, pattern, graph, p_v_emb, p_e_emb, g_v_emb, g_e_emb, v_gate=
     np_, ep_ = pattern.number_of_nodes(), pattern.number_of_edges()
     union = _union_of(pattern, graph)
     l0 = _layer0_codes(union, layers, p_v_emb, p_e_emb, g_v_emb, g_e_emb, v_gate, e_gate, np_)
+    vg, eg = _joint_gates(v_gate, e_gate, np_, ep_, p_e_emb.dtype, p_e_emb.device)
     v = None
     if l0 is not None:        # the first layer works on the label codes: its [E, H] input rows are only its residual term
-        from . import fused
         # ... which the layer reads over the kept edges' / nodes' tiles only: the rows under a zero of a 0 / 1 gate are not even stored
-        # (the degree coefficients the test below asks about: memoised, the layers ask for the same -- made here when the
-        # prefetch did not, so that a step without the side stream takes the same launches as one with it)
-        if OUTDEGREE not in union.ndata:
-            union.ndata[OUTDEGREE] = union.out_degrees()
-        union.index().degree_coef(union.ndata[OUTDEGREE])
-        live_e, live_v = fused.l0_dead_inputs(union.index(), layers[0].hidden_dim, *_joint_gates(v_gate, e_gate, np_, ep_, p_e_emb.dtype, p_e_emb.device),
-                                              l0)
-        l0.z_from_codes = fused.l0_z_from_codes(union.index(), layers[0].hidden_dim, _joint_gates(v_gate, e_gate, np_, ep_, p_e_emb.dtype, p_e_emb.device)[1],
-                                                l0, live_e, model.rep_residual)
+        # (the coefficients: those the layers ask for, made here when the prefetch did not -- the same launches with and without it)
+        H = layers[0].hidden_dim
+        ix, coef = _joint_index(union)
+        live_e, live_v = fused.l0_dead_inputs(ix, H, vg, eg, l0, coef)
+        l0.z_from_codes = fused.l0_z_from_codes(ix, H, eg, l0, live_e, model.rep_residual)
         with th.no_grad():
             if l0.z_from_codes:     # ... or not stored at all: the layer's second Linear forms the kept rows from the codes in registers
                 l0.z_head = p_e_emb.detach()          # (the pattern's rows: few, embedded by their own table)
-                e = fused.dead_rows_buffer((ep_ + g_e_emb._dmp_src[0].size(0), layers[0].hidden_dim), p_e_emb.device)
+                e = fused.dead_rows_buffer((ep_ + g_e_emb._dmp_src[0].size(0), H), p_e_emb.device)
             else:
                 e = _GateConcat.apply(p_e_emb, None, e_gate, g_e_emb._dmp_src[0], g_e_emb._dmp_src[1], live_e)
             if l0.venc is not None:
@@ -503,12 +488,9 @@ def joint_rep(model, pattern, graph, p_v_emb, p_e_emb, g_v_emb, g_e_emb, v_gate=
         e = _gate_concat(p_e_emb, g_e_emb, e_gate)
     if v is None:
         v = _gate_concat(p_v_emb, g_v_emb, v_gate)   # [pattern rows | gate * target rows] in one pass
-    vg, eg = _joint_gates(v_gate, e_gate, np_, ep_, v.dtype, v.device)
-    from . import side
     if not all(l.fused_ok(union, v, e, vg, eg) for l in layers):     # e.g. dropout in training: the callers run the two loops
         side.join()
         return None
-    from . import fused
     folded = fused.fold_layers(layers)                       # the parameter algebra of all layers: one launch
     side.wait("index")                                       # (prefetch_joint_indexes: the union's CSR, coefficients, selectors)
     sums = (None, None)

@@ -183,10 +183,8 @@ def keep_pool_csr(pool, gate):
     chunk CSR), memoised on the gate per index, or None.  A pooled pass with a 0 / 1 row weight is then the PLAIN segment sum
     over 42 % of the entries (full load slots) instead of the weighted one that walks every entry: 46 -> 28 us at bench.py's
     shape; same sums, same order (the skipped rows added zeros)."""
-    if gate is None or not USE_ROW_MASKS or pool.num_chunks == 0 or gate.numel() == 0:
-        return None
-    own = gatememo.owner(gate)
-    if not gatememo.skips_rows(own, True):
+    own = None if gate is None else gatememo.owner(gate)
+    if not has_row_mask(own, True, True) or pool.num_chunks == 0 or gate.numel() == 0:
         return None
     return gatememo.memo(own, ("keep_pool", id(pool)), (pool,), lambda: _csr_keep(pool.vptr, pool.vent, gate, pool.num_chunks), True)
 
@@ -372,10 +370,8 @@ def masked_slots(index, coef, gate):
     None (no gate, masks off, a gate known to be dense).  For kernels whose streamed rows are ZERO for such edges -- ``dPre``
     of a gated layer: ``atb_typed`` skips the edge, ``bwd_z_typed`` skips the fetch of its ``dPre`` row.  Memoised on the gate
     (shared by the layers of a rep-net) per slot list."""
-    if gate is None or not USE_ROW_MASKS:
-        return None
-    own = gatememo.owner(gate)
-    if gatememo.flag(own, "dense", True):
+    own = None if gate is None else gatememo.owner(gate)
+    if not has_row_mask(own, resolved=True):
         return None
     slot_edge = index.class_tiles(coef)[0]
 
@@ -395,10 +391,8 @@ def live_tiles(index, coef, gate):
     a zero gate has no slot at all, so the kernels walk 46 % of the tiles of a ScalarFilter batch instead of all of them with
     padding slots inside), or None -- a gate not flagged 0 / 1, masks off, a coefficient of unknown origin.  For the launches
     that LEAVE OUT such edges (``masked_slots`` turns them into padding where every edge needs its slot).  Memoised on the gate."""
-    if gate is None or not USE_ROW_MASKS or not USE_LIVE_TILES:
-        return None
-    own = gatememo.owner(gate)
-    if not gatememo.skips_rows(own, True):
+    own = None if gate is None else gatememo.owner(gate)
+    if not live_tiles_ok(index, coef, own):
         return None
     return gatememo.memo(own, "live_tiles", (index, coef), lambda: index.class_tiles_gated(coef, gate.reshape(-1)), True)
 
@@ -406,10 +400,8 @@ def live_tiles(index, coef, gate):
 def keep_in_csr(index, gate):
     """``(keep_ptr, keep_ent)``: ``index``'s CSR by destination over the edges a 0 / 1 ``gate`` keeps (``dmp_csr_keep``), memoised
     on the gate (the layers of a rep-net share it), or None."""
-    if gate is None or not USE_ROW_MASKS or index.num_edges == 0:
-        return None
-    own = gatememo.owner(gate)
-    if not gatememo.skips_rows(own, True):
+    own = None if gate is None else gatememo.owner(gate)
+    if index.num_edges == 0 or not has_row_mask(own, True, True):
         return None
     return gatememo.memo(own, "keep_in_csr", (index,), lambda: _csr_keep(index.in_ptr, index.in_ent, gate, index.num_nodes), True)
 
@@ -633,10 +625,8 @@ def dead_rows_buffer(shape, device):
 def gate_row_mask(gate):
     """uint32 [(R + 31) // 32]: bit r of word t = (gate[32 t + r] != 0) (``dmp_row_mask_bits``), for the ``_masked`` kernels;
     memoised on the gate tensor (a layer's forward and backward, and every layer of a rep-net, share the gate)."""
-    if gate is None or not USE_ROW_MASKS:
-        return None
-    own = gatememo.owner(gate)
-    if gatememo.flag(own, "dense", True):            # a gate its maker knows to be (almost) all ones: nothing to skip
+    own = None if gate is None else gatememo.owner(gate)
+    if not has_row_mask(own, resolved=True):
         return None
 
     def build():
@@ -957,10 +947,8 @@ def zero_rows_gate(gate):
     ``dmpnn.joint_rep``: the union's edge rows are ``[pattern rows | gate * target rows]``): every layer's input rows under a
     zero of the gate are zeros -- ``zn = z + gate (...)`` (dmpnn.py:215-277) keeps them so -- and sums over rows may leave
     them out."""
-    if gate is None or not USE_MASKED_SUMS or not USE_ROW_MASKS:
-        return False
-    own = gatememo.owner(gate)
-    return bool(gatememo.skips_rows(own, True) and gatememo.flag(own, "zero_rows", True))
+    own = None if gate is None else gatememo.owner(gate)
+    return bool(USE_MASKED_SUMS and has_row_mask(own, True, True) and gatememo.flag(own, "zero_rows", True))
 
 
 def binary_gate_mask(gate):
@@ -969,6 +957,52 @@ def binary_gate_mask(gate):
     if gate is None or not USE_PLAIN_ATB or not gatememo.flag(gate, "binary"):
         return None
     return gate_row_mask(gate)
+
+
+# ---- the dead-row conditions of a joint pass.  A row that one launch leaves unwritten must be left out by every reader, so each
+# verdict is stated ONCE, here: host tests of the index's sizes, H, the gates' marks and the switches as they stand at the call (no
+# launch, no memo build), asked by the layer's forward and backward, ``l0_dead_inputs`` and ``dmpnn.prefetch_joint_indexes``.
+def has_row_mask(gate, binary=False, resolved=False):
+    """``gate_row_mask(gate) is not None``, without building it; ``binary``: ... and flagged 0 / 1 (the kept-row lists, tiles, CSRs)."""
+    own = gate if resolved or gate is None else gatememo.owner(gate)
+    return bool(own is not None and USE_ROW_MASKS and (gatememo.skips_rows(own, True) if binary else not gatememo.flag(own, "dense", True)))
+
+
+def dead_h1_rows(index, H, e_gate):
+    """The rows of the edge MLP's activation H1e under a zero of ``e_gate`` are DEAD: their producers leave them out, every
+    consumer (out_fwd / the pooled passes; bwd_h1, atb_rows, pool_relu_bwd) multiplies them by that zero without fetching."""
+    return bool(SKIP_DEAD_ROWS and has_row_mask(e_gate) and typed_ok(index, H))
+
+
+def live_tiles_ok(index, coef, gate):
+    """``live_tiles(index, coef, gate) is not None``, without building them (``coef``: ``index``'s own, built from its integer degrees)."""
+    src = getattr(index, "_coef_deg", None)
+    return bool(USE_LIVE_TILES and has_row_mask(gate, binary=True) and src is not None and src[0] is coef and index.num_edges > 0)
+
+
+def dead_edge_rows(index, H, e_gate, coef=None):
+    """... and so are the layer's INPUT edge rows and their gradient rows (``zero_rows_gate``): not fetched, not computed.  With
+    ``coef``: nor, in an inner layer, written -- the class-tile launches walk ``live_tiles``, which can be built."""
+    own = None if e_gate is None else gatememo.owner(e_gate)      # (resolved once: the layers ask this several times per pass)
+    return dead_h1_rows(index, H, own) and zero_rows_gate(own) and (coef is None or live_tiles_ok(index, coef, own))
+
+
+def kept_node_path(index, H, v_gate, l0=None, min_nodes=4096):
+    """A layer's node side runs on the nodes the 0 / 1 ``v_gate`` keeps (``node_rows``; from ``min_nodes`` nodes on: below, the
+    dense launches are as fast).  ``l0``: the first layer on the label codes -- its backward's row masks start at a table's first node."""
+    N = index.num_nodes
+    return bool(USE_NODE_ROWS and USE_PLAIN_ATB and N >= min_nodes and index.num_edges > 0 and typed_ok(index, H) and zero_rows_gate(v_gate)
+                and not (l0 is not None and any(n0 % 32 for _, _, (n0, _) in l0.tables(index.num_edges, N))))
+
+
+def l0_row_list(r0, rows):
+    """The first layer's launches over the ``rows`` edge rows from ``r0`` on walk a kept-row list (``kept_rows``) of their mask."""
+    return bool(USE_L0_ROW_LISTS and r0 % 32 == 0 and rows >= L0_LIST_MIN_ROWS)
+
+
+def kept_incidence_sums(index, H, e_gate, kept_nodes):
+    """The backward's endpoint sums run over ``NodeRows.kept_incidence`` (``kept_nodes``: ``kept_node_path`` held)."""
+    return bool(kept_nodes and dead_edge_rows(index, H, e_gate))
 
 
 def bwd_h1_mfma(d_o, W2, h1, coef=None, index=None, both_halves=True, gate=None, out=None, slope=0.0, rows_colsum=False,
@@ -1290,12 +1324,9 @@ def node_rows(index, v_gate, H):
     rep-net's input node rows by it (``zero_rows_gate``: the rows under its zeros are zeros in EVERY layer, dmpnn.py:245-277,
     so for such a node v the aggregate A[v], the projections P[v], node_out[v] and every gradient row of v are dead), the
     tile kernels take the shape.  Memoised on the gate (the layers of a rep-net share it).  Else None."""
-    if (not USE_NODE_ROWS or not USE_PLAIN_ATB or v_gate is None or not zero_rows_gate(v_gate) or not typed_ok(index, H)
-            or index.num_edges == 0):
+    if not kept_node_path(index, H, v_gate, min_nodes=0):      # (the list itself can be built for any number of nodes)
         return None
     mask = gate_row_mask(v_gate)
-    if mask is None:
-        return None
 
     def build():
         N = index.num_nodes
@@ -1354,7 +1385,7 @@ def l0_edge_fwd(enc, K, M, P, ldp, bias, coef, index, slope=0.0, rows=None, out=
     sel_a, sel_b, coef_e = index.edge_select(coef)
     if mask is not None and r0 % 32 != 0:
         mask = None
-    if mask is not None and USE_L0_ROW_LISTS and r1 - r0 >= L0_LIST_MIN_ROWS:
+    if mask is not None and l0_row_list(r0, r1 - r0):
         lst, cnt = kept_rows(mask, r0, r1)
         with _lib.timed("l0_edge_fwd[K=%d,E=%d]", (K, r1 - r0), 4 * H * (r1 - r0 + min(2 * index.num_nodes, 2 * (r1 - r0))) + (4 * enc.size(1) + 12) * (r1 - r0)):
             check(lib.dmp_l0_edge_fwd_rows(ptr(enc[r0:]), enc.stride(0), K, ptr(M), M.stride(0), ptr(P), ldp, ptr(bias), ptr(coef_e[r0:]),
@@ -1385,7 +1416,7 @@ def l0_bwd_w(enc, K, coef_e, d_pre, d_zn=None, rows=None, out=None, mask=None):
     nacc = (3 if d_zn is not None else 2) * K
     G = int(lib.dmp_l0_bwd_w_blocks(r1 - r0))
     part = torch.empty((G, nacc * H), dtype=torch.float32, device=d_pre.device)
-    if mask is not None and USE_L0_ROW_LISTS and r1 - r0 >= L0_LIST_MIN_ROWS:
+    if mask is not None and l0_row_list(0 if own else r0, r1 - r0):
         lst, cnt = kept_rows(mask, 0, r1 - r0) if own else kept_rows(mask, r0, r1)
         with _lib.timed("l0_bwd_w[K=%d,E=%d]", (K, r1 - r0), 4 * (H * (2 if d_zn is not None else 1) + enc.size(1) + 1) * (r1 - r0)):
             check(lib.dmp_l0_bwd_w_rows(ptr(enc[r0:]), enc.stride(0), K, ptr(coef_e[r0:]), ptr(d_pre[r0:]), d_pre.stride(0),
@@ -1720,9 +1751,7 @@ class _FusedDMPLayer(torch.autograd.Function):
         # the node side runs on the kept nodes' tiles, the edge kernels read a dead node's (unwritten) rows as zeros
         from . import side      # (index builds issued ahead on the side stream, dmpnn.prefetch_joint_indexes: wait for a stage at its first use)
         side.wait("nodes")
-        nd = node_rows(index, v_gate, H) if (N >= 4096 and onepanel_ok(H)) else None
-        if nd is not None and l0 is not None and any(n0 % 32 for _, _, (n0, _) in l0.tables(z.size(0), N)):
-            nd = None          # (the backward's row masks start at a table's first node)
+        nd = node_rows(index, v_gate, H) if kept_node_path(index, H, v_gate, l0) else None
         # ---- node side (dmpnn.py:113,121,125 + fn.sum + 129-140)
         S0 = M0 = tables = None
         chained, chain_panels = False, None
@@ -1847,17 +1876,14 @@ class _FusedDMPLayer(torch.autograd.Function):
         # ---- edge side (dmpnn.py:112,120,124 + 142-156)
         sums_only = epool is not None and not edge_rows
         zn = None
-        # H1e rows under a zero edge gate are DEAD values when the layer runs on the masked kernels: out_fwd / the pooled
-        # passes forward and bwd_h1 / atb_rows / pool_relu_bwd backward all multiply them by that zero and do not fetch them
-        # (typed_ok: the backward takes the same branch).  The two producers then leave those rows out.
         side.wait("erows" if l0 is not None else "tiles")      # (a layer on the label codes needs the tiles only for its second Linear)
-        dead_gate = e_gate if (SKIP_DEAD_ROWS and USE_ROW_MASKS and e_gate is not None and typed_ok(index, H)
-                               and gate_row_mask(e_gate) is not None) else None
+        dead_gate = e_gate if dead_h1_rows(index, H, e_gate) else None     # (the two producers of H1e leave its dead rows out)
+        dead_in = dead_gate is not None and dead_edge_rows(index, H, e_gate)
         # the one-launch edge MLP stands exactly where the route below is edge_fwd_typed + out_fwd_typed over the kept edges' tiles
         # (dead == 3 with live_tiles and the folded W2^T): a gated INNER layer whose edge rows are wanted, with its residual
         mlp_tiles = None
-        if (l0 is None and dead_gate is not None and not sums_only and residual and eW2t is not None and (inner & 1)
-                and zero_rows_gate(e_gate) and edge_mlp_fwd_ok(H, z, PXr, eW2t)):
+        if (l0 is None and dead_in and not sums_only and residual and eW2t is not None and (inner & 1)
+                and edge_mlp_fwd_ok(H, z, PXr, eW2t)):
             mlp_tiles = live_tiles(index, coef, e_gate)
         if l0 is not None:
             H1e = dead_rows_buffer((z.size(0), H), z.device) if dead_gate is not None else torch.empty((z.size(0), H), dtype=torch.float32, device=z.device)
@@ -1888,7 +1914,7 @@ class _FusedDMPLayer(torch.autograd.Function):
             # a gate whose maker wiped the rep-net's input rows (zero_rows_gate): z's rows under its zeros are zeros -- not
             # fetched; as an INNER layer of a rep-net (``inner``: the next layer of the same rep-net, under the same gate,
             # is the only reader of zn) the output's zero rows are not stored either
-            dead = (3 if (inner & 1) else 1) if (dead_gate is not None and zero_rows_gate(e_gate)) else 0
+            dead = (3 if (inner & 1) else 1) if dead_in else 0
             side.wait("tiles")
             lt = live_tiles(index, coef, e_gate) if (dead == 3 and eW2t is not None) else None
             if lt is not None:      # nothing to write for the rows under a zero gate: the kept edges' tiles only
@@ -1992,8 +2018,7 @@ class _FusedDMPLayer(torch.autograd.Function):
                 if H % 4 == 0 and H <= 256:
                     # (dPre's rows under a zero of a 0 / 1 gate: every reader below leaves them out -- the kept incidence sums,
                     # the class-tile kernels over the kept edges' tiles)
-                    skip = (typed and USE_MASKED_SUMS and SKIP_DEAD_ROWS and ctx.l0 is None and binary_gate_mask(ctx.e_gate) is not None
-                            and zero_rows_gate(ctx.e_gate) and live_tiles(ix, coef, ctx.e_gate) is not None and nd is not None)
+                    skip = ctx.l0 is None and nd is not None and USE_PLAIN_ATB and dead_edge_rows(ix, H, ctx.e_gate, coef)
                     dG, dbe, Q = pool_relu_bwd(T @ eW2, emap, ctx.e_gate, H1e, ep, slope, skip_dead=skip)       # dG is dPre; one pass over H1e
                     Q = Q[:, :H]
                 else:
@@ -2012,7 +2037,7 @@ class _FusedDMPLayer(torch.autograd.Function):
                     # gradient runs ungated over the masked-in rows on the bf16 pipe
                     # (dPre's zero rows are not stored: the class-tile kernels, the scatter-add and the layer-0 products below
                     # leave them out)
-                    skip = (USE_MASKED_SUMS and SKIP_DEAD_ROWS and gate_row_mask(ctx.e_gate) is not None
+                    skip = (USE_MASKED_SUMS and dead_h1_rows(ix, H, ctx.e_gate)
                             and (ctx.l0 is None or getattr(ctx.l0, "enc_mask", None) is not None))
                     lt = live_tiles(ix, coef, ctx.e_gate) if skip else None
                     if lt is not None and h1w_ok(dzn, H1e, H):
@@ -2048,9 +2073,9 @@ class _FusedDMPLayer(torch.autograd.Function):
             # [dPn | dP]: written in place, no concatenation (under ``nd``: the kept nodes' rows only)
             dXP = dead_rows_buffer((N, 3 * H), x.device) if nd is not None else torch.empty((N, 3 * H), dtype=torch.float32, device=x.device)
             # dPre into both endpoints' rows: the backward scatter-add (dPre's rows under a zero edge gate are zeros: not fetched)
-            sums_masked = typed and USE_MASKED_SUMS and ctx.e_gate is not None and gate_row_mask(ctx.e_gate) is not None
+            sums_masked = typed and USE_MASKED_SUMS and has_row_mask(ctx.e_gate)
             # (... and the rows of the dead nodes are neither summed nor stored)
-            if nd is not None and sums_masked and zero_rows_gate(ctx.e_gate) and H % 4 == 0:
+            if kept_incidence_sums(ix, H, ctx.e_gate, nd is not None):
                 # every kept node's two sums over its KEPT edges (the incidence CSR over the kept edges, a row per kept node):
                 # the plain segment-sum kernel, ascending edge id -- an edge row without a kept endpoint is never fetched
                 kp, ke = nd.kept_incidence(ix, ctx.e_gate)
@@ -2080,7 +2105,7 @@ class _FusedDMPLayer(torch.autograd.Function):
                 # (with the input gradient still to come -- ``dz`` below, over the same tile list -- both products of dPre run in ONE
                 # launch there, ``bwd_z_w``: decided here, made there)
                 fuse_dzw = bool(typed and ctx.needs_input_grad[4] and H == 128 and
-                                (ctx.e_gate is None or (SKIP_DEAD_ROWS and zero_rows_gate(ctx.e_gate) and live_tiles(ix, coef, ctx.e_gate) is not None)))
+                                (ctx.e_gate is None or dead_edge_rows(ix, H, ctx.e_gate, coef)))
                 dWes = None if fuse_dzw else (atb_typed(z, dG, coef, ix, gate=ctx.e_gate) if typed else atb(z, dG))   # [H,2H] = [dA_e | dB_e]
             # ---- node side
             wg = (lambda a, b: atb_rows(a, b, colsum=False)[0]) if atb_ok(x, dXP) else atb   # MFMA kernel or library GEMMs
@@ -2215,7 +2240,7 @@ class _FusedDMPLayer(torch.autograd.Function):
                 # the input gradient of an edge under a zero of a gate that wiped the rep-net's input rows is multiplied by that
                 # zero further down: not computed.  After the first layer (``inner`` bit 1) its reader is the layer before,
                 # which leaves those rows out; the first layer hands zeros to whoever made the rows.
-                dead_dz = (("leave" if (ctx.inner & 2) else "zero") if (typed and SKIP_DEAD_ROWS and zero_rows_gate(ctx.e_gate)) else None)
+                dead_dz = (("leave" if (ctx.inner & 2) else "zero") if dead_edge_rows(ix, H, ctx.e_gate) else None)
                 dst_m = None if nd is None else nd.sel[2]      # (dS's rows of the dead nodes were not written: read as zeros)
                 both = None
                 if typed and dWes is None:
@@ -2271,20 +2296,13 @@ def l0_z_from_codes(index, H, eg, l0, live_edges, residual):
                 and index.num_edges * 128 * 4 < (1 << 32) - 65536)
 
 
-def l0_dead_inputs(index, H, vg, eg, l0):
+def l0_dead_inputs(index, H, vg, eg, l0, coef):
     """``(edges, nodes)``: may the input rows of a first layer on the label codes (``l0``) stay UNWRITTEN under the zeros of the
     union's 0 / 1 gates?  The layer reads its edge rows ``z`` only as the residual term of its second Linear -- over the kept
-    edges' tiles when the conditions below hold (the ones ``_FusedDMPLayer.forward`` tests) -- and its node rows ``x`` (with
-    node codes) only as the residual term over the kept nodes' tiles."""
-    if l0 is None or not SKIP_DEAD_ROWS or not USE_ROW_MASKS or not typed_ok(index, H):
-        return False, False
-    edges = bool(eg is not None and zero_rows_gate(eg) and gate_row_mask(eg) is not None and USE_LIVE_TILES
-                 and getattr(index, "_coef_deg", None) is not None)
-    N = index.num_nodes
-    nodes = bool(l0.venc is not None and vg is not None and USE_NODE_ROWS and USE_PLAIN_ATB and N >= 4096 and onepanel_ok(H) and zero_rows_gate(vg)
-                 and gate_row_mask(vg) is not None and index.num_edges > 0
-                 and not any(n0 % 32 for _, _, (n0, _) in l0.tables(index.num_edges, N)))
-    return edges, nodes
+    edges' tiles under ``dead_edge_rows`` -- and its node rows ``x`` (with node codes) only as the residual term over the kept
+    nodes' tiles (``kept_node_path``)."""
+    return (l0 is not None and dead_edge_rows(index, H, eg, coef),
+            bool(l0 is not None and l0.venc is not None and kept_node_path(index, H, vg, l0)))
 
 
 def activation_slope(act):

@@ -165,3 +165,39 @@ def test_row_mask_miss_on_the_main_stream_waits_for_the_side_stream(gpu):
     th.cuda.synchronize()
     bits = ((mask.view(-1, 1).to(th.int64) >> th.arange(32, device=gpu)) & 1).reshape(-1)[:R].float()
     assert th.equal(bits, src)
+
+
+# the memoised products of one forward + backward that a CONSUMER builds on the main stream, in build order: none, with lazy edge
+# rows and without -- all fourteen (the union's gates, both row masks, three kept-row lists, the kept nodes' selectors and tiles, the
+# kept edges' tiles, ascending tiles, CSR, pooling CSR, gate sums and incidence CSR) come from ``dmpnn.prefetch_joint_indexes``
+CONSUMER_BUILT = []
+
+
+@pytest.mark.parametrize("lazy", [True, False])
+def test_the_prefetch_builds_what_the_consumers_look_up(lazy, gpu):
+    """The drift guard of the dead-row conditions: at the smallest batch of ``bench.CFG`` at which every one of them holds, a
+    product that the prefetch's condition leaves out (or hangs elsewhere than its consumer looks) shows up as a memo build on
+    the main stream -- the builds made outside the fork are exactly ``CONSUMER_BUILT``."""
+    from dualmessagepassing_amd import fused, gatememo, side
+    bench_, cfg, shard, step, model, run = _setup(gpu, batch=64)
+    p, g = shard["p"], shard["g"]
+    assert p["N"] + g["N"] == 4608 >= 4096 and g["E"] == 32768 >= fused.L0_LIST_MIN_ROWS and p["E"] == 1536 and p["E"] % 32 == 0
+    assert side.USE_SIDE_STREAM
+    built = []
+    real = gatememo.memo
+
+    def spy(holder, name, keys, build, resolved=False):
+        def recorded():
+            # (a pooling index's entry carries the index's id, the union's gates their dtype and version: the kind alone)
+            built.append((name[0] if isinstance(name, tuple) and name[0] in ("keep_pool", "joint_gates") else name, side.active()))
+            return build()
+        return real(holder, name, keys, None if build is None else recorded, resolved)
+
+    gatememo.memo = spy
+    try:
+        run(bench_, cfg, shard, step, model, lazy)
+    finally:
+        gatememo.memo = real
+    print("memo builds (name, on the side stream):", built)
+    assert any(on for _, on in built), "the prefetch did not run"
+    assert [n for n, on in built if not on] == CONSUMER_BUILT
