@@ -384,4 +384,9 @@ SIGNATURES = {
     "dmp_lrp_fill": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
     "dmp_rank_supported": (c_int, [c_int]),
     "dmp_rank_counts": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
+    "dmp_lrp_pool_supported": (c_int, [c_int, c_int, c_int]),
+    "dmp_lrp_pool_workspace_words": (c_size, [c_i64, c_int, c_int, c_int]),
+    "dmp_lrp_pool_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "dmp_lrp_pool_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_ptr,
+                                 c_ptr, c_ptr, c_ptr, c_ptr]),
 }

@@ -15,6 +15,9 @@ the pooling matrix averages a CONTIGUOUS range of permutations per node (dataset
     out  = rows.view(P, L*L*in) @ weight.permute(2, 0, 1).reshape(L*L*in, hid)     one dense product, K = 16 in
     node = scale[:, None] * seg_pool(out, ranges)                  the segment-sum kernel over contiguous ranges
 
+At widths 64 / 128 the first two lines are one launch sequence of csrc/dmp_lrppool.hip (``perm_product``, ``USE_POOL_KERNEL``):
+the rows are gathered inside the kernels, forward and backward, and no [P * L*L, in] matrix exists.
+
 ``PermIndex`` holds the slot vector / ranges / scales of a batch; it is built from the reference's three sparse
 tensors (``from_sparse``: what ``LRPDataset.batchify`` hands over), from the ego-net permutations enumerated on the host
 (``from_graphs``) or from the batched graph itself on the device (``from_batched``: csrc/dmp_lrp.hip, count -> scan -> fill).
@@ -48,6 +51,7 @@ class PermIndex:
         self.num_perms = int(slot.numel()) // (seq_len * seq_len)
         self._pool = None
         self._csr = None
+        self._key_csr = None
         self.status = None      # from_batched: int64 [1] on the device, the OR of the DMP_LRP_* bits
         self.live = None        # an index padded to a capacity: float [num_perms], 1 for the real permutations, 0 for the tail
 
@@ -238,6 +242,27 @@ class PermIndex:
             self._csr = (self.slot.to(th.int32), rowptr, ent)
         return self._csr
 
+    def key_csr(self):
+        """``(rowptr, entp)`` of the pool kernels' table gradient: the CSR of the slots by the key ``slot * L*L + s`` over
+        ``(N + E) * L*L`` rows -- one row per (table row, slot position) -- with the permutation of every entry, ascending
+        inside a row.  A slot that reads the zero row has a key past the last row and stays behind ``rowptr[-1]``.
+        ``(None, None)`` for an index without permutations.  One stable sort of the keys: ``dmp_csr_build`` sorts every row
+        with one thread, and a hub's slot 0 -- every permutation of the node, 1,716 entries at 13 neighbours -- made that
+        2.1 ms per index at 9 x 10^5 slots."""
+        if self._key_csr is None:
+            L2 = self.seq_len * self.seq_len
+            M, rows, dev = int(self.slot.numel()), (self.num_nodes + self.num_edges) * L2, self.slot.device
+            if M == 0:
+                self._key_csr = (None, None)
+                return self._key_csr
+            key = self.slot * L2
+            key.view(self.num_perms, L2).add_(th.arange(L2, device=dev))
+            key, order = th.sort(key, stable=True)                                     # equal keys: ascending entry = ascending p
+            rowptr = th.searchsorted(key, th.arange(rows + 1, device=dev)).to(th.int32)
+            self._key_csr = (rowptr, th.div(order, L2, rounding_mode="floor").to(th.int32))   # entry p * L*L + s -> p
+        _lib.pin_for_capture(*self._key_csr)
+        return self._key_csr
+
     def pool_index(self):
         if self._pool is None:
             self._pool = ops.PoolIndex(self.sizes, num_rows=self.num_perms)
@@ -278,15 +303,80 @@ class _SlotRows(th.autograd.Function):
         return g[:ctx.N], g[ctx.N:], None
 
 
-def perm_pool(perm, node_feat, edge_feat, weight, bias=None, act=None):
-    """``pooling @ act(einsum(slots(node_feat, edge_feat), weight) + bias)`` (lrp.py:66-73 / dmplrp.py:188-194 with
-    ``act`` None): gather, one dense product over the L*L slots, per-node segment sum, scale."""
+# True: ``perm_pool`` takes the product before bias and activation on the pool kernels (csrc/dmp_lrppool.hip: no
+# [P * L*L, in] matrix in either pass) wherever they admit the shape; False: gather, dense product, segment sum.
+USE_POOL_KERNEL = True
+
+
+class _PermProduct(th.autograd.Function):
+    """``einsum(slots(node_feat, edge_feat), weight)`` [P, hid] on the pool kernels: the rows are gathered inside them,
+    forward and backward; the backward's table gradient runs over ``PermIndex.key_csr``.  ``calls``: forward launches so
+    far (what a test reads to see which route ran)."""
+
+    calls = 0
+
+    @staticmethod
+    def forward(ctx, node_feat, edge_feat, weight, perm):
+        lib = _lib.load()
+        _lib.require_gpu(node_feat, edge_feat, weight, perm.slot)
+        x, z, w = node_feat.contiguous(), edge_feat.contiguous(), weight.contiguous()
+        P, L, fin, hid = perm.num_perms, perm.seq_len, w.size(0), w.size(1)
+        out = th.empty((P, hid), dtype=th.float32, device=x.device)
+        ws = th.empty(int(lib.dmp_lrp_pool_workspace_words(P, fin, hid, L)), dtype=th.int32, device=x.device)
+        with _lib.timed("lrp_pool_fwd[in=%d,hid=%d,L=%d,P=%d]", (fin, hid, L, P),
+                        4 * (P * hid + (x.size(0) + z.size(0)) * fin + w.numel()) + 8 * P * L * L):
+            _lib.check(lib.dmp_lrp_pool_fwd(_lib.ptr(x), _lib.ptr(z), _lib.ptr(w), _lib.ptr(perm.slot), P, perm.num_nodes, perm.num_edges,
+                                            fin, hid, L, _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()), "dmp_lrp_pool_fwd")
+        ctx.save_for_backward(x, z, w)
+        ctx.perm = perm
+        _PermProduct.calls += 1
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        lib = _lib.load()
+        x, z, w = ctx.saved_tensors
+        perm = ctx.perm
+        P, L, fin, hid = perm.num_perms, perm.seq_len, w.size(0), w.size(1)
+        d = d.contiguous()
+        rowptr, entp = perm.key_csr()
+        dx, dz, dw = th.empty_like(x), th.empty_like(z), th.empty_like(w)
+        ws = th.empty(int(lib.dmp_lrp_pool_workspace_words(P, fin, hid, L)), dtype=th.int32, device=x.device)
+        with _lib.timed("lrp_pool_bwd[in=%d,hid=%d,L=%d,P=%d]", (fin, hid, L, P),
+                        4 * (2 * P * hid + 2 * (x.size(0) + z.size(0)) * fin + 2 * w.numel()) + 12 * P * L * L):
+            _lib.check(lib.dmp_lrp_pool_bwd(_lib.ptr(x), _lib.ptr(z), _lib.ptr(w), _lib.ptr(perm.slot), _lib.ptr(rowptr), _lib.ptr(entp),
+                                            _lib.ptr(d), P, perm.num_nodes, perm.num_edges, fin, hid, L, _lib.ptr(dx), _lib.ptr(dz),
+                                            _lib.ptr(dw), _lib.ptr(ws), _lib.stream_ptr()), "dmp_lrp_pool_bwd")
+        return dx, dz, dw, None
+
+
+def _pool_kernel_ok(perm, node_feat, edge_feat, weight):
+    """The shapes ``dmp_lrp_pool_fwd`` / ``_bwd`` admit: fp32 on the GPU, widths 64 / 128, index sizes inside int32."""
     L2 = perm.seq_len * perm.seq_len
-    if node_feat.size(0) != perm.num_nodes or edge_feat.size(0) != perm.num_edges:
-        raise ValueError("perm_pool: the permutation index was built for %d nodes / %d edges" % (perm.num_nodes, perm.num_edges))
+    return (weight.dim() == 3 and weight.size(2) == L2 and node_feat.size(1) == edge_feat.size(1) == weight.size(0)
+            and all(t.is_cuda and t.dtype == th.float32 for t in (node_feat, edge_feat, weight)) and perm.slot.is_cuda
+            and (perm.num_perms + 64) * L2 < (1 << 31) and (perm.num_nodes + perm.num_edges + 32) * L2 + 1 < (1 << 31)
+            and bool(_lib.load().dmp_lrp_pool_supported(weight.size(0), weight.size(1), perm.seq_len)))
+
+
+def perm_product(perm, node_feat, edge_feat, weight):
+    """``einsum(slots(node_feat, edge_feat), weight)`` [P, hid], the product over the L*L slots before bias and activation: on
+    the pool kernels where they admit the shape (``USE_POOL_KERNEL``), else one row gather and one dense product."""
+    L2 = perm.seq_len * perm.seq_len
+    if USE_POOL_KERNEL and _pool_kernel_ok(perm, node_feat, edge_feat, weight):
+        return _PermProduct.apply(node_feat, edge_feat, weight, perm)
     rows = _SlotRows.apply(node_feat, edge_feat, perm)                            # [P * L*L, in]
     w = weight.permute(2, 0, 1).reshape(L2 * weight.size(0), weight.size(1))      # [(slot, in), hid]
-    out = ops.matmul_xw(rows.view(perm.num_perms, L2 * weight.size(0)), w)
+    return ops.matmul_xw(rows.view(perm.num_perms, L2 * weight.size(0)), w)
+
+
+def perm_pool(perm, node_feat, edge_feat, weight, bias=None, act=None):
+    """``pooling @ act(einsum(slots(node_feat, edge_feat), weight) + bias)`` (lrp.py:66-73 / dmplrp.py:188-194 with
+    ``act`` None): the product over the L*L slots (``perm_product``), per-node segment sum, scale."""
+    if node_feat.size(0) != perm.num_nodes or edge_feat.size(0) != perm.num_edges:
+        raise ValueError("perm_pool: the permutation index was built for %d nodes / %d edges" % (perm.num_nodes, perm.num_edges))
+    out = perm_product(perm, node_feat, edge_feat, weight)
     if bias is not None:
         out = out + bias
     if act is not None:

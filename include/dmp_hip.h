@@ -1616,6 +1616,29 @@ int dmp_rank_supported(int H);
 int dmp_rank_counts(const float *query, const float *table, const int64_t *target, const int64_t *filt_ptr, const int64_t *filt_idx,
                     int64_t nnz, int64_t Q, int64_t N, int H, int32_t *greater, int32_t *equal, void *stream);
 
+/* ---- The permutation product of an LRP / DMPLRP layer without its gathered slot rows (dmp_lrppool.hip; lrp.py:66-73,
+ * dmplrp.py:188-194: the two sparse selections and einsum('dab,bca->dc')), before bias and activation:
+ *   out[p, :] = sum_s row(slot[p, s]) W_s,   row(t) = node_feat[t] (t < N), edge_feat[t - N] (t < N + E), else 0,
+ *   W_s = weight[:, :, s]   (weight [in, hid, L L] as the reference keeps it; slot [P L L] as dmp_lrp_fill writes it)
+ *   dweight[:, :, s] = sum_p row(slot[p, s])^T dout[p],   dnode / dedge [t] = sum_{(p, s): slot[p, s] = t} dout[p] W_s^T
+ * node_feat [N, in], edge_feat [E, in], out / dout [P, hid], dnode [N, in], dedge [E, in]: fp32, contiguous, 16-byte aligned.
+ * Nothing of P L L in (or hid) floats is read, written or needed: the feature rows are gathered inside the kernels, a tile of
+ * 32 permutations skips the slots none of them fills, and the L L panels are split into bf16 pieces once per call (six piece
+ * products per block: fp32-accurate).  No float atomics, fixed summation order: bitwise repeatable.
+ *   rowptr  [(N + E) L L + 1] int32: CSR of the slots by the key  slot[p, s] L L + s  over (N + E) L L rows (a slot that
+ *           reads the zero row has a key outside them and belongs to no row)
+ *   entp    int32: the permutation p of every CSR entry, ascending inside a row (the order of the sums: keep it fixed)
+ *   ws      dmp_lrp_pool_workspace_words(P, in, hid, L) 32-bit words (from the shapes alone), 16-byte aligned
+ * Admitted: dmp_lrp_pool_supported(in, hid, L) -- in, hid in {64, 128}, 1 <= L <= DMP_LRP_MAX_SEQ_LEN -- P >= 0, and
+ * (P + 64) L L, (N + E + 32) L L + 1 < 2^31; else DMP_ERR_UNSUPPORTED (0 words), decided before any launch. */
+int dmp_lrp_pool_supported(int in, int hid, int L);
+size_t dmp_lrp_pool_workspace_words(int64_t P, int in, int hid, int L);
+int dmp_lrp_pool_fwd(const float *node_feat, const float *edge_feat, const float *weight, const int64_t *slot, int64_t P, int64_t N,
+                     int64_t E, int in, int hid, int L, float *out, int32_t *ws, void *stream);
+int dmp_lrp_pool_bwd(const float *node_feat, const float *edge_feat, const float *weight, const int64_t *slot, const int32_t *rowptr,
+                     const int32_t *entp, const float *dout, int64_t P, int64_t N, int64_t E, int in, int hid, int L, float *dnode,
+                     float *dedge, float *dweight, int32_t *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

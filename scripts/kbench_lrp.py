@@ -12,7 +12,9 @@ entry by entry first.
 Step: ``train_epoch`` over the same batches, eager (exact totals) and through ``GraphedTrainStep`` (padded batches,
 capacity levels), each on its own copy of the model, warmed first, alternating windows; device events around windows
 that end in a synchronise.  Peak memory: the rise of ``torch.cuda.max_memory_allocated`` over a way's warm-up (for the
-replayed way that is where the recordings' memory pools are allocated), above what was allocated before it."""
+replayed way that is where the recordings' memory pools are allocated), above what was allocated before it.
+The result also names the route ``perm_pool`` took (``perm_pool_route``) and, after the timed windows, the launch timer's
+per-kernel times of ONE eager step of the first batch (``eager_step_kernels``)."""
 import argparse
 import copy
 import json
@@ -87,6 +89,8 @@ def bench_step(a, view, dev):
         sync = FlatGradSync(model)
         opt = FlatAdamW([sync.flatten_parameters()], lr=1e-4, weight_decay=1e-5, amsgrad=True, capturable=True)
         step = GraphedTrainStep(model, opt, sync, max_shapes=4) if way == "replay" else None
+        if way == "eager":
+            eager_parts = (model, opt, sync)
         runs[way] = (lambda model=model, opt=opt, sync=sync, step=step: train_epoch(model, opt, ds, B, dev, sync=sync, neg_slp=0.01, graph=step), step)
     times, peak = {way: [] for way in runs}, {}
     replay = runs["replay"][1]
@@ -112,7 +116,33 @@ def bench_step(a, view, dev):
                     "steps": len(ts) * a.batches, "peak_memory_above_start_mib": peak[way]}
     res["replay"]["replays"], res["replay"]["eager_calls"] = replay.steps.replays, replay.steps.eager_calls
     res["speedup"] = res["eager"]["ms_per_step_median"] / res["replay"]["ms_per_step_median"]
+    res["eager_step_kernels"] = step_kernels(ds, B, dev, *eager_parts)
     return res
+
+
+def pool_route():
+    """Which way ``perm_pool`` takes its product on this tree at the widths of this run."""
+    from dualmessagepassing_amd import lrp
+    return "pool_kernel" if getattr(lrp, "USE_POOL_KERNEL", False) else "slot_rows"
+
+
+def step_kernels(ds, B, dev, model, opt, sync):
+    """Per-kernel launch times of ONE eager DMPLRP step (the first batch; the model is warm) from the launch timer: record
+    name -> launches / total us, the five largest first, and their sum.  Taken after the timed windows: the events cost time."""
+    from dualmessagepassing_amd import _lib
+    from dualmessagepassing_amd.harness import train_epoch
+    one = ds.subset(range(B))
+    _lib.timer.reset()
+    _lib.timer.enabled = True
+    try:
+        train_epoch(model, opt, one, B, dev, sync=sync, neg_slp=0.01)
+        summary = _lib.timer.summary()
+    finally:
+        _lib.timer.enabled = False
+        _lib.timer.reset()
+    rows = sorted(((name, s["launches"], s["avg_us_all"] * s["launches"]) for name, s in summary.items()), key=lambda r: -r[2])
+    return {"timed_launches_total_us": sum(r[2] for r in rows), "launches": sum(r[1] for r in rows),
+            "kernels": [{"name": n, "launches": k, "total_us": us} for n, k, us in rows]}
 
 
 def main():
@@ -130,7 +160,7 @@ def main():
     dev = th.device("cuda:0")
     view = SmallLikePairs(a.batch * a.batches, seed=1).lrp(a.seq_len)
     res = {"batch": a.batch, "lrp_seq_len": a.seq_len, "hid_dim": 64, "max_distinct_degree": view.max_degree,
-           "index": bench_index(a, view, dev)}
+           "perm_pool_route": pool_route(), "index": bench_index(a, view, dev)}
     if not a.skip_step:
         res["step"] = bench_step(a, view, dev)
     line = json.dumps(res)
