@@ -32,6 +32,7 @@ DMP_MEM_MEAN, DMP_MEM_SUM, DMP_MEM_MAX = 0, 1, 2      # the pooling modes of dmp
 DMP_LRP_MAX_NEIGHBOURS = 32                            # distinct out-neighbours of a node the permutation index admits
 DMP_LRP_MAX_SEQ_LEN = 6
 DMP_LRP_OVER_CAP, DMP_LRP_SELF_LOOP, DMP_LRP_DROPPED = 1, 2, 4      # bits of the status word of dmp_lrp_count / _fill
+DMP_RANK_BAD_TYPE = 1                                  # status word of dmp_rank_counts_typed: a type code above 62 was met
 
 
 # ---- the structs, named and ordered as in the header; pointers are c_void_p (assigned from ``data_ptr()`` / None)
@@ -384,6 +385,9 @@ SIGNATURES = {
     "dmp_lrp_fill": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
     "dmp_rank_supported": (c_int, [c_int]),
     "dmp_rank_counts": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
+    "dmp_rank_typed_workspace_words": (c_size, [c_i64]),
+    "dmp_rank_counts_typed": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr,
+                                      c_ptr, c_ptr, c_ptr]),
     "dmp_lrp_pool_supported": (c_int, [c_int, c_int, c_int]),
     "dmp_lrp_pool_workspace_words": (c_size, [c_i64, c_int, c_int, c_int]),
     "dmp_lrp_pool_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),

@@ -31,6 +31,43 @@ def load_links(path):
     return np.asarray(rows, dtype=np.int64).reshape(len(rows), -1), num_nodes, num_rels
 
 
+def load_nodes(path):
+    """The dataset's original ``node.dat``, one ``id<TAB>name<TAB>type[<TAB>comma-separated attributes]`` row per node (the
+    columns the reference's ``Transform/transform_model.py`` reads as ``line[0]``, ``line[2]``, ``line[3]``), in any order of
+    the ids.  Returns ``(node_type int64 [N], attributes float32 [N, A] or None)`` as torch tensors indexed by node id, N =
+    the largest id + 1: the types ``evaluate_links(node_type=...)`` ranks by, the attributes ``TrainModel(node_attri=...)``
+    takes.  A converted two-column file (``id<TAB>attributes``) carries no type and is refused."""
+    ids, types, attrs = [], [], []
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            line = line.rstrip("\n")
+            if not line.strip():
+                continue
+            cols = line.split("\t")
+            if len(cols) < 3:
+                raise ValueError("%s line %d has %d tab-separated column(s): a node.dat with a type column (id, name, type[, "
+                                 "attributes]) is needed, a converted id/attributes file has none" % (path, n, len(cols)))
+            ids.append(int(cols[0]))
+            types.append(int(cols[2]))
+            attrs.append([float(v) for v in cols[3].split(",")] if len(cols) > 3 and cols[3].strip() else None)
+    if not ids:
+        raise ValueError("%s lists no node" % (path,))
+    ids = np.asarray(ids, dtype=np.int64)
+    N = int(ids.max()) + 1
+    if ids.min() < 0 or len(np.unique(ids)) != len(ids) or len(ids) != N:
+        raise ValueError("%s: the ids are 0 .. N - 1, each once (got %d rows, largest id %d)" % (path, len(ids), N - 1))
+    node_type = np.empty(N, dtype=np.int64)
+    node_type[ids] = np.asarray(types, dtype=np.int64)
+    have = [a is not None for a in attrs]
+    if not any(have):
+        return torch.from_numpy(node_type), None
+    if not all(have) or len({len(a) for a in attrs}) != 1:
+        raise ValueError("%s: every node carries the same number of attributes, or none does" % (path,))
+    attributes = np.empty((N, len(attrs[0])), dtype=np.float32)
+    attributes[ids] = np.asarray(attrs, dtype=np.float32)
+    return torch.from_numpy(node_type), torch.from_numpy(attributes)
+
+
 def save_embeddings(path, embeddings, index=None, header=""):
     """The reference's output file (utils.py:243-258): a header line, then ``node_id<TAB>v0 v1 ...`` per node."""
     emb = np.asarray(embeddings)
@@ -256,12 +293,17 @@ def split_links(triplets, test_fraction, seed):
 
 
 @torch.no_grad()
-def evaluate_links(model, graph, train_triplets, test_triplets, known=None, filtered=True, ks=(1, 3, 10), ties="mean", **sampling):
+def evaluate_links(model, graph, train_triplets, test_triplets, known=None, filtered=True, ks=(1, 3, 10), ties="mean",
+                   node_type=None, by_relation=False, **sampling):
     """Rank the held-out ``test_triplets`` with the model's own decoder: ``collect_node_embeddings`` over the training
     graph (``sampling``: its keyword arguments), then ``unc_eval.link_ranks`` / ``link_metrics`` with ``model.w_relation``,
     both sides.  ``filtered``: every other known true entity of a query leaves its candidates -- ``known`` [M, 3], by
     default training + test links.  For every encoder ``unc.TrainModel`` builds and for ``unc_compgcn.TrainModel``.
-    -> the metrics dict (one host sync besides the sampling's)."""
+    ``node_type`` [N] (``load_nodes``): the type-constrained protocol of ``unc_eval.link_ranks`` -- every query against the
+    node types its relation joins on that side, read off training + test links (off ``known`` when given) -- and the dict
+    also carries ``candidates`` and ``AMRI``.  ``by_relation``: the block of ``unc_eval.link_metrics_by_relation`` under
+    ``"relation/<r>/"`` as well (one more host sync).
+    -> the metrics dict (one host sync besides the sampling's and the index building's)."""
     from . import unc_eval
     w_relation = getattr(model, "w_relation", None)
     if w_relation is None:
@@ -274,5 +316,15 @@ def evaluate_links(model, graph, train_triplets, test_triplets, known=None, filt
     model.train(was_training)
     if filtered and known is None:
         known = torch.cat([train_triplets, test_triplets])
-    ranks = unc_eval.link_ranks(w_relation, node_emb, test_triplets, known=known if filtered else None, ties=ties)
-    return unc_eval.link_metrics(ranks, ks=ks)
+    if node_type is None:
+        ranks = unc_eval.link_ranks(w_relation, node_emb, test_triplets, known=known if filtered else None, ties=ties)
+        out = unc_eval.link_metrics(ranks, ks=ks)
+    else:
+        seen = known if known is not None else torch.cat([train_triplets, test_triplets])
+        masks = unc_eval.relation_type_masks(seen, node_type, w_relation.size(0))
+        ranks, considered = unc_eval.link_ranks(w_relation, node_emb, test_triplets, known=known if filtered else None, ties=ties,
+                                                node_type=node_type, type_masks=masks, return_considered=True)
+        out = unc_eval.link_metrics(ranks, ks=ks, considered=considered)
+    if by_relation:
+        out.update(unc_eval.link_metrics_by_relation(ranks, test_triplets[:, 1], w_relation.size(0), ks=ks))
+    return out

@@ -1616,6 +1616,25 @@ int dmp_rank_supported(int H);
 int dmp_rank_counts(const float *query, const float *table, const int64_t *target, const int64_t *filt_ptr, const int64_t *filt_idx,
                     int64_t nnz, int64_t Q, int64_t N, int H, int32_t *greater, int32_t *equal, void *stream);
 
+/* The same counts against the candidates of the node types a query admits (dmp_rank_typed.hip; the type-constrained protocol of
+ * heterogeneous graphs, where a relation joins a fixed pair of node types):
+ *   C_i = {c : c != target[i], c not in filt_i, bit cand_type[c] of allowed[i] set},   considered[i] = |C_i|
+ * greater / equal as above over this C_i; t_i is the target's score whatever the target's type is, and every score is the same
+ * fmaf chain as dmp_rank_counts computes.  cand_type [N]: type codes 0 .. 62; allowed [Q]: bit t = type t is admitted (bit 63
+ * is ignored).  tile_types: workspace of dmp_rank_typed_workspace_words(N) words, sized by N alone and written anew by
+ * every call: a pre-pass stores per tile of 128 candidates the OR of 1 << type over its rows (a workgroup reduce, no atomics),
+ * and the ranking kernel neither fetches nor multiplies a tile whose word does not meet the types its 128 query rows admit.
+ * Right for any order of the candidates and of the queries; it skips most where the candidates are ordered by type and the
+ * queries by mask.  Two launches on the stream, no host sync, integer atomics only: bitwise repeatable.
+ * Errors: a NULL cand_type / allowed / tile_types is DMP_ERR_BAD_ARG.  A type code above 62 lies in device memory, where the
+ * host cannot see it without a sync: such a candidate is admitted by no query, and the device word `status` (or NULL: not
+ * wanted), zeroed by the call, receives DMP_RANK_BAD_TYPE -- the status-word convention of dmp_lrp_count. */
+#define DMP_RANK_BAD_TYPE 1
+size_t dmp_rank_typed_workspace_words(int64_t N);
+int dmp_rank_counts_typed(const float *query, const float *table, const int64_t *target, const int64_t *filt_ptr, const int64_t *filt_idx,
+                          int64_t nnz, const uint8_t *cand_type, const uint64_t *allowed, int64_t Q, int64_t N, int H, int32_t *greater,
+                          int32_t *equal, int32_t *considered, uint64_t *tile_types, int64_t *status, void *stream);
+
 /* ---- The permutation product of an LRP / DMPLRP layer without its gathered slot rows (dmp_lrppool.hip; lrp.py:66-73,
  * dmplrp.py:188-194: the two sparse selections and einsum('dab,bca->dc')), before bias and activation:
  *   out[p, :] = sum_s row(slot[p, s]) W_s,   row(t) = node_feat[t] (t < N), edge_feat[t - N] (t < N + E), else 0,
