@@ -725,17 +725,26 @@ def out_codes_ok(h1, enc, K, Wc):
                 and enc.size(0) == h1.size(0) and h1.size(0) * 128 * 4 < lim and Wc.stride(1) == 1)
 
 
-def out_fwd_typed_codes(h1, W2t, b2, enc, K, Wc, tiles, prev=None, out=None, w_in_out=True, row0=0):
+def out_fwd_typed_codes(h1, W2t, b2, enc, K, Wc, tiles, prev=None, out=None, w_in_out=True, row0=0, first=None):
     """``prev + (h1 W2^T + enc[:, :K] Wc + b2)`` for the rows of ``tiles`` (``dmp_out_fwd_typed_codes``): the second Linear of a FIRST
     layer whose residual rows are the label embedding ``enc Wc`` -- added as one more 16-deep k-group of the product, so the [E, H] rows
     ``z0`` are neither written (``dmp_smallk_embed_live``) nor read.  ``row0``: the rows below it take no codes term (the pattern's
-    edges, embedded by another table); ``prev`` may then hold just those rows ([row0 or more, H]: missing rows count as zeros)."""
+    edges, embedded by another table); ``prev`` may then hold just those rows ([row0 or more, H]: missing rows count as zeros).
+    ``first``: ``h1`` does not exist yet -- the keyword arguments of the layer's first Linear on the same codes (``M, tables, split, P,
+    ldp, bias, coef, index, slope`` of ``l0_edge_fwd``, ``M`` holding every table's rows, the rows below ``split`` being the first
+    table's) whose output it is: both Linears then run as ONE launch over ``tiles`` (``dmp_l0_edge_mlp_fwd``, through ``l0_edge_fwd``),
+    which fills ``h1`` on the way."""
     lib = _lib.load()
     slot_edge, tile_scale, num_tiles, bound = tiles
     R, H = h1.shape
     if out is None:
         out = dead_rows_buffer((R, H), h1.device)
     Wc = Wc.detach()
+    if first is not None:
+        l0_edge_fwd(enc, K, first["M"], first["P"], first["ldp"], first["bias"], first["coef"], first["index"], first["slope"], out=h1,
+                    mlp=dict(tables=first["tables"], split=first["split"], W2t=W2t, b2=b2, Wc=Wc, row0=row0, prev=prev, tiles=tiles,
+                             w_in_out=w_in_out, out=out))
+        return out
     _lib.require_gpu(h1, W2t, out, prev, b2, enc, Wc)
     j = _abi.dmp_typed_job()
     j.Hin, j.ldh, j.W2, j.ldw, j.w_in_out = h1.data_ptr(), h1.stride(0), W2t.data_ptr(), W2t.stride(0), int(bool(w_in_out))
@@ -779,7 +788,11 @@ USE_EDGE_MLP_FWD = True   # a gated inner layer's edge MLP forward over the kept
 def edge_mlp_fwd_ok(H, *tensors):
     """``edge_mlp_fwd`` applies: H = 128, the bf16x6 arithmetic, fp32 operands with unit column stride in rows of whole 16-byte pieces,
     arrays below 4 GiB.  Otherwise the two launches (``edge_fwd_typed`` / ``out_fwd_typed``) run."""
-    if not USE_EDGE_MLP_FWD or H != 128 or _lib.load().dmp_dev_get_exact_fp32():
+    return bool(USE_EDGE_MLP_FWD and _one_launch_mlp_operands_ok(H, tensors))
+
+
+def _one_launch_mlp_operands_ok(H, tensors):
+    if H != 128 or _lib.load().dmp_dev_get_exact_fp32():
         return False
     lim = (1 << 32) - 65536
     for a in tensors:
@@ -789,6 +802,17 @@ def edge_mlp_fwd_ok(H, *tensors):
                 or a.data_ptr() % 16 or a.size(0) * a.stride(0) * 4 >= lim):
             return False
     return True
+
+
+USE_L0_EDGE_MLP = True    # the first layer's edge MLP forward from the label codes as one launch (csrc/dmp_l0mlp.hip) instead of one per table + one
+
+
+def l0_edge_mlp_ok(H, K, tables, *tensors):
+    """The one-launch form of ``l0_edge_fwd`` + ``out_fwd_typed_codes`` applies: H = 128, the bf16x6 arithmetic, at most two embedding
+    tables of at most ``dmp_l0_edge_mlp_max_codes()`` code columns, fp32 operands with unit column stride in rows of whole 16-byte
+    pieces, arrays below 4 GiB.  Otherwise the launches of their own run."""
+    return bool(USE_L0_EDGE_MLP and 1 <= tables <= 2 and 1 <= K <= _lib.load().dmp_l0_edge_mlp_max_codes()
+                and _one_launch_mlp_operands_ok(H, tensors))
 
 
 def edge_mlp_fwd(z, Wes, P, ldp, bias, coef, index, slope, W2t, b2, prev, tiles, sel=None, w_in_out=True, h1=None, out=None):
@@ -1372,17 +1396,36 @@ def l0_node_fwd(venc, VK, S0, K0, Kp, W, bias, slope, mask, n0, n1, H, h1, P, ro
                                   ptr(h1), h1.stride(0), ptr(P), P.stride(0), stream_ptr()), "dmp_l0_node_fwd")
 
 
-def l0_edge_fwd(enc, K, M, P, ldp, bias, coef, index, slope=0.0, rows=None, out=None, mask=None):
+def l0_edge_fwd(enc, K, M, P, ldp, bias, coef, index, slope=0.0, rows=None, out=None, mask=None, mlp=None):
     """``act(enc M[:, :H] + coef[dst] enc M[:, H:] + P[a, 0:H] - P[b, H:2H] + bias)`` -- ``edge_fwd_typed`` for input rows
     ``enc W`` of rank K with ``M = W Wes``: no class tiles, rows in their own order.  ``rows = (r0, r1)``: only that range
     of the edge rows (written into ``out[r0:r1]``): rows of another embedding table take another ``M``.  ``mask`` (a
-    ``gate_row_mask`` over all E rows): its zero bits mark DEAD output rows, left out entirely."""
+    ``gate_row_mask`` over all E rows): its zero bits mark DEAD output rows, left out entirely.
+    ``mlp``: the layer's second Linear rides in the same launch (``dmp_l0_edge_mlp_fwd``, see ``out_fwd_typed_codes(first=...)``):
+    ``M`` then holds the ``mlp["tables"]`` tables' rows (rows below ``mlp["split"]``: the first table's), the launch walks
+    ``mlp["tiles"]`` -- rows outside them are neither read nor written -- and also fills ``mlp["out"]`` (a selector of -1 reads zeros there)."""
     lib = _lib.load()
     E, H = enc.size(0), M.size(1) // 2
     if out is None:
         out = torch.empty((E, H), dtype=torch.float32, device=enc.device)
     r0, r1 = (0, E) if rows is None else rows
     sel_a, sel_b, coef_e = index.edge_select(coef)
+    if mlp is not None:
+        slot_edge, _, num_tiles, bound = mlp["tiles"]
+        W2t, b2, Wc, prev, zn = mlp["W2t"], mlp["b2"], mlp["Wc"], mlp["prev"], mlp["out"]
+        tables = int(mlp["tables"])
+        split = int(mlp["split"]) if tables == 2 else 0
+        _lib.require_gpu(enc, M, P, bias, W2t, b2, Wc, prev, out, zn)
+        # (the record form of the first of the launches this one replaces, at the second table's row count: bench.py prices the
+        # names it knows at the kept rows)
+        with _lib.timed("l0_edge_fwd[K=%d,E=%d]", (K, E - split), 4 * H * (E + min(2 * index.num_nodes, 2 * E)) + (4 * enc.size(1) + 12) * E):
+            check(lib.dmp_l0_edge_mlp_fwd(ptr(enc), enc.stride(0), int(K), ptr(M), M.stride(0), tables, split, ptr(P), ldp, index.num_nodes,
+                                          ptr(bias), ptr(coef_e), ptr(sel_a), ptr(sel_b), float(slope), ptr(W2t), W2t.stride(0),
+                                          int(bool(mlp.get("w_in_out", True))), ptr(b2), ptr(Wc), Wc.stride(0), int(mlp["row0"]), ptr(prev),
+                                          prev.stride(0) if prev is not None else H, 0 if prev is None else min(E, prev.size(0)),
+                                          ptr(slot_edge), ptr(num_tiles), bound, E, H, ptr(out), out.stride(0), ptr(zn), zn.stride(0),
+                                          stream_ptr()), "dmp_l0_edge_mlp_fwd")
+        return out
     if mask is not None and r0 % 32 != 0:
         mask = None
     if mask is not None and l0_row_list(r0, r1 - r0):
@@ -1887,10 +1930,32 @@ class _FusedDMPLayer(torch.autograd.Function):
             mlp_tiles = live_tiles(index, coef, e_gate)
         if l0 is not None:
             H1e = dead_rows_buffer((z.size(0), H), z.device) if dead_gate is not None else torch.empty((z.size(0), H), dtype=torch.float32, device=z.device)
-            for t, rows, _ in tables:
-                if rows[1] > rows[0]:
-                    l0_edge_fwd(enc0, K0, M0[t * K0:(t + 1) * K0], PXr, ldpx, be, coef, index, slope, rows, H1e,
-                                mask=gate_row_mask(dead_gate) if dead_gate is not None else None)
+            # the one-launch edge MLP stands exactly where the route is l0_edge_fwd per table + out_fwd_typed_codes (below): over the
+            # kept edges' tiles under the gates (whose zero rows are dead rows of H1e: the per-table launches leave them out as well,
+            # where their mask starts at a whole word), over the identity tiles without a gate
+            l0_tiles = None
+            if (not sums_only and residual and eW2t is not None and getattr(l0, "z_from_codes", False)
+                    and out_codes_ok(H1e, l0.enc, l0.K, W0[-l0.K:])
+                    and l0_edge_mlp_ok(H, K0, W0.size(0) // K0, enc0, PXr, eW2t, l0.z_head)):
+                if dead_in and (inner & 1):
+                    side.wait("tiles")
+                    lt = live_tiles(index, coef, e_gate)
+                    if lt is not None:
+                        l0_tiles = ascending_tiles(e_gate) or lt
+                elif e_gate is None:
+                    # (212 against 275 us for the launches of their own; the first build was time-neutral here: docs/HISTORY.md (oo))
+                    l0_tiles = identity_tiles(H1e.size(0), H1e.device)
+            if l0_tiles is not None:
+                # both Linears as ONE launch: H1e goes from the first to the second on the chip, the code rows are fetched once
+                # (through the second Linear's wrapper, as every E-row Linear + residual launch goes: it fills H1e on the way)
+                zn = out_fwd_typed_codes(H1e, eW2t, eb2, l0.enc, l0.K, W0[-l0.K:], l0_tiles, prev=l0.z_head, row0=l0.z_head.size(0),
+                                         first=dict(M=M0, tables=W0.size(0) // K0, split=l0.esplit, P=PXr, ldp=ldpx, bias=be, coef=coef,
+                                                    index=index, slope=slope))
+            else:
+                for t, rows, _ in tables:
+                    if rows[1] > rows[0]:
+                        l0_edge_fwd(enc0, K0, M0[t * K0:(t + 1) * K0], PXr, ldpx, be, coef, index, slope, rows, H1e,
+                                    mask=gate_row_mask(dead_gate) if dead_gate is not None else None)
         elif mlp_tiles is not None:
             # both Linears over the kept edges' class tiles as ONE launch: H1e goes from the first to the second on the chip
             # (through the second Linear's wrapper, as every E-row Linear + residual launch goes: it fills H1e on the way)

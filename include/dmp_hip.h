@@ -1279,6 +1279,27 @@ int dmp_edge_mlp_fwd(const float *Z, int64_t ldz, const float *W, int64_t ldw, c
                      float *out, int64_t ldo, void *stream);
 
 /*
+ * The FIRST layer's edge MLP forward from the label codes over a tile list in ascending row order (the kept edges' tiles, or the
+ * identity list) as ONE launch (csrc/dmp_l0mlp.hip) -- dmp_l0_edge_fwd_rows / _masked for every embedding table AND
+ * dmp_out_fwd_typed_codes:
+ *     H1[e]  = act(enc[e, 0:K] MA_t + coefE[e] (enc[e, 0:K] MB_t) + P[selA e, 0:H] - P[selB e, H:2H] + bias1)
+ *              M [tables K, ldm >= 2H], rows t K .. t K + K - 1 = [MA_t | MB_t]; t = 0 for e < row_split, 1 otherwise (tables = 1: t = 0)
+ *     out[e] = (e < r_rows ? R[e] : 0) + (H1[e] W2 + (e >= code_row0 ? enc[e, 0:K] Wc : 0) + bias2)
+ * for the edges e of the tile list; nothing is read, computed or stored for any other edge, and a selector of -1 reads zeros.  A
+ * 512-thread workgroup per CU: four waves form H1 on the matrix pipe ([enc | coefE enc] against the stacked matrices, bf16x6) and
+ * hand every tile on as bf16 pieces in LDS together with its code rows, four waves form `out` from them as dmp_out_fwd_typed_codes
+ * does (bit-identical on every kept row).  H1 is stored once (the backward needs it) and never read back; the code rows are fetched
+ * once.  H = 128, bf16x6, K <= dmp_l0_edge_mlp_max_codes(), tables <= 2, arrays below 4 GiB; DMP_ERR_UNSUPPORTED otherwise (callers
+ * run the launches it replaces).
+ */
+int dmp_l0_edge_mlp_max_codes(void);
+int dmp_l0_edge_mlp_fwd(const float *enc, int64_t lde, int K, const float *M, int64_t ldm, int tables, int64_t row_split, const float *P,
+                        int64_t ldp, int64_t num_nodes, const float *bias1, const float *coefE, const int32_t *selA, const int32_t *selB,
+                        float slope, const float *W2, int64_t ldw2, int w2_in_out, const float *bias2, const float *Wc, int64_t ldwc,
+                        int64_t code_row0, const float *R, int64_t ldr, int64_t r_rows, const int32_t *slot_edge, const int32_t *num_tiles,
+                        int64_t tiles_bound, int64_t num_edges, int H, float *H1, int64_t ldh, float *out, int64_t ldo, void *stream);
+
+/*
  * Input gradient of the edge chain in one pass (replaces dmp_gather_select + the K=2H GEMM):
  *     dZ[e] = base[e] + s(flag e) * D[dst e, (flag e ? H : 0) + :] + dPre[e] W[:, 0:H]^T
  *             + coefE[e] * dPre[e] W[:, H:2H]^T
