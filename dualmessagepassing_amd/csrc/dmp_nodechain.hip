@@ -6,11 +6,13 @@
 //
 // Both are six [rows, 128] x [128, 128] products on row-local operands.  The tile kernels of dmp_typed.hip keep ONE weight panel
 // in registers, so such a chain is three dependent launches with partial sums going through memory.  Here the ROWS stay put and
-// the PANELS stream: a 512-thread workgroup (one per CU) owns a contiguous range of the tile list and walks it 4 tiles = 128
-// rows at a time; the rows' current operand sits in LDS as three bf16 planes (the image of dmp_typed.hip, 104,448 bytes), the
-// 128 x 128 fp32 result block in registers (wave w: tile w / 2, columns 64 (w & 1) ..: 2 x 16 accumulators per lane), and the
+// the PANELS stream: a 256-thread workgroup (two per CU) owns a contiguous range of the tile list and walks it 2 tiles = 64
+// rows at a time; the rows' current operand sits in LDS as three bf16 planes (the image of dmp_typed.hip, 52,224 bytes), the
+// 64 x 128 fp32 result block in registers (wave w: tile w / 2, columns 64 (w & 1) ..: 2 x 16 accumulators per lane), and the
 // six panels -- split into their bf16 pieces ONCE per step by dmp_node_chain_pack, in fragment order -- come from L2 through two
-// 24 KiB LDS buffers, a quarter of a panel (32 k) per step, the next quarter requested before the current one multiplies.
+// 12 KiB LDS buffers, one k-group of a panel (16 k) per step, requested two steps ahead into a ring of two register sets.
+// A workgroup still waits at most steps' end; the CU's two workgroups share no barrier, so one multiplies while the other
+// waits (docs/HISTORY.md (pp)).
 // A product's result that is the next product's operand (H1n, dPn) goes from the accumulators straight into the LDS image.
 //
 // Summation order is fixed (k-groups ascending inside a panel, panels in the order above; the column-sum partials through
@@ -23,14 +25,23 @@ __device__ int llvm_struct_buffer_load_i32(i32x4 rsrc, int vindex, int voffset, 
 __device__ void llvm_struct_buffer_store_i32(int data, i32x4 rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.buffer.store.i32");
 namespace {
 
-constexpr int kChainThreads = 512;
-constexpr int kChainRows = 128;                               // rows per pass of a workgroup: 4 tiles
+constexpr int kChainTiles = 2;                                // tiles per pass of a workgroup (even): two waves per tile
+constexpr int kChainThreads = 128 * kChainTiles;              // 256
+constexpr int kChainRows = 32 * kChainTiles;                  // rows per pass of a workgroup: 64
+constexpr int kChainStageRows = kChainThreads / 32;           // rows one staging sweep covers (32 float4 per row): 8 sweeps per pass
 constexpr int kChainStrideD = 68;                             // dwords per image row: 128 bf16 + 8 of padding (dmp_typed.hip)
 constexpr int kChainPlane = kChainRows * kChainStrideD;       // dwords per piece plane
-constexpr int kChainImageBytes = 3 * kChainPlane * 4;         // 104,448
+constexpr int kChainImageBytes = 3 * kChainPlane * 4;         // 52,224
 constexpr int kChainPanelBytes = 3 * 128 * 128 * 2;           // 98,304: [k-group 8][piece 3][column block 4][lane 64][8 bf16]
-constexpr int kChainChunkBytes = kChainPanelBytes / 4;        // 24,576: two k-groups
-constexpr int kChainLdsBytes = kChainImageBytes + 2 * kChainChunkBytes + kChainRows * 4;   // 154,112 of the CU's 163,840
+constexpr int kChainGroupBytes = kChainPanelBytes / 8;        // 12,288: one k-group
+constexpr int kChainChunkGroups = kChainTiles / 2;            // k-groups per step: every thread fetches 3 x 16 bytes of them
+constexpr int kChainChunkBytes = kChainChunkGroups * kChainGroupBytes;      // 12,288
+constexpr int kChainSteps = 8 / kChainChunkGroups;            // steps per panel (even: a panel starts in buffer 0)
+constexpr int kChainLdsBytes = kChainImageBytes + 2 * kChainChunkBytes + kChainRows * 4;   // 77,056: two workgroups in the CU's 163,840
+constexpr int kChainBlocksPerCU = 163840 / kChainLdsBytes;    // 2
+constexpr int kChainCUs = 256;
+constexpr int kChainMaxBlocks = kChainCUs * kChainBlocksPerCU;      // every CU's share resident at once: 512
+static_assert(kChainTiles % 2 == 0 && kChainSteps % 2 == 0 && kChainChunkBytes == 3 * kChainThreads * 16, "chunk = one 3 x 16-byte fetch per thread");
 constexpr int kChainMaxPanels = 12;
 
 __device__ __forceinline__ float sbuf_load1(srsrc_t r, int row, uint32_t col_bytes) {
@@ -87,7 +98,7 @@ struct ChainArgs {
 };
 
 template <bool BWD, bool FULL>
-__global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
+__global__ __launch_bounds__(kChainThreads, kChainBlocksPerCU) void node_chain_k(ChainArgs p) {
   extern __shared__ __attribute__((aligned(256))) unsigned char lds[];
   uint32_t *Aimg = reinterpret_cast<uint32_t *>(lds);
   unsigned char *Pb = lds + kChainImageBytes;
@@ -97,10 +108,10 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lane = t & 63, li = lane & 31, h = lane >> 5;
   const int rt = wave >> 1, ch = wave & 1;                    // this wave's tile of the pass and its 64-column half
-  const int q = t & 31, r0 = t >> 5;                          // staging: float4 q of rows r0 + 16 m
+  const int q = t & 31, r0 = t >> 5;                          // staging: float4 q of rows r0 + kChainStageRows m
   const float slope = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.slope)));
   const bool has_res = p.Res != nullptr;
-  const int NC = __builtin_amdgcn_readfirstlane(p.npanels) * 4;      // quarter panels per pass
+  const int NC = __builtin_amdgcn_readfirstlane(p.npanels) * kChainSteps;      // chunks per pass
   constexpr bool full = FULL;                                 // backward: dx wanted (forward: always)
 
   const int ntiles = __builtin_amdgcn_readfirstlane(*p.num_tiles);
@@ -121,10 +132,10 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
 
   int ids[8];
   float4 pre[8];
-  auto load_ids = [&](int tile0) {                            // slots of the 4 tiles from tile0; past the range's end: -1
+  auto load_ids = [&](int tile0) {                            // slots of the pass's tiles from tile0; past the range's end: -1
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
-      const int idx = tile0 * kSub + r0 + 16 * m;
+      const int idx = tile0 * kSub + r0 + kChainStageRows * m;
       const int v = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_slot, idx * 4, 0, 0);
       ids[m] = idx < hi * kSub ? v : -1;
     }
@@ -137,7 +148,7 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
   auto stage = [&](bool first) {                              // pre -> the image (split once, here); first: the pass's ids too
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
-      const int row = r0 + 16 * m;
+      const int row = r0 + kChainStageRows * m;
       if (BWD && first) { csA.x += pre[m].x; csA.y += pre[m].y; csA.z += pre[m].z; csA.w += pre[m].w; }
       uint2 ph, pm, pl;
       split_pair(pre[m].x, pre[m].y, ph.x, pm.x, pl.x);
@@ -155,31 +166,48 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
   };
-  // one panel = four steps: request the next quarter (of this panel, the next one, or the next pass's first), multiply the
-  // current one (two k-groups x two column blocks x six piece products), store the requested quarter into the other buffer
+  // one panel = kChainSteps steps.  The chunks go through a ring of two register sets into the two LDS buffers: a step requests
+  // the chunk TWO steps ahead (of this panel, the next one, or the next pass's first two) -- fenced, so that the request is issued
+  // ahead of the step's MFMAs in every instantiation --, multiplies the current one (its k-groups x two column blocks x six piece
+  // products), then stores the chunk requested a step earlier into the other buffer: the wait in front of that store leaves the
+  // newest request in flight.  The CU's other workgroup, a phase apart, multiplies while this one waits -- but between two
+  // waves of a SIMD the OLDER one wins every issue slot, so the workgroup that came second to a CU would run in the first one's
+  // gaps only and finish a third later (docs/HISTORY.md (pp)).  The two therefore take the higher priority in turn, a product
+  // each: workgroups b and b + kChainCUs share a CU when the grid fills the chip (a guess about placement that costs nothing
+  // where it is wrong).
+  uint4 pc[2][3];
+  const int second = __builtin_amdgcn_readfirstlane((int)blockIdx.x / kChainCUs & 1);
+  auto request = [&](int set, int c) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_pan, (i * kChainThreads + t) * 16, c * kChainChunkBytes, 0);
+      pc[set][i] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+  };
   auto product = [&](int pidx) {
 #pragma unroll
-    for (int cc = 0; cc < 4; ++cc) {
-      const int c = 4 * pidx + cc;
-      const int nc = c + 1 == NC ? 0 : c + 1;
-      uint4 pc[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_pan, (i * kChainThreads + t) * 16, nc * kChainChunkBytes, 0);
-        pc[i] = make_uint4(v.x, v.y, v.z, v.w);
+    for (int cc = 0; cc < kChainSteps; ++cc) {
+      const int c = kChainSteps * pidx + cc;
+      const int nc = c + 2 >= NC ? c + 2 - NC : c + 2;
+      if (cc == 0) {
+        if ((pidx + second) & 1) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
       }
+      __builtin_amdgcn_sched_barrier(0);
+      request(cc & 1, nc);
+      __builtin_amdgcn_sched_barrier(0);
       const unsigned char *pb = Pb + (cc & 1) * kChainChunkBytes;
       const uint32_t *ar = Aimg + (32 * rt + li) * kChainStrideD + 32 * h;
 #pragma unroll
-      for (int gl = 0; gl < 2; ++gl) {
-        const int g = 2 * cc + gl;
+      for (int gl = 0; gl < kChainChunkGroups; ++gl) {
+        const int g = kChainChunkGroups * cc + gl;
         Split8 a;
         a.hi.v = *reinterpret_cast<const bf16x8 *>(ar + 4 * g);
         a.mid.v = *reinterpret_cast<const bf16x8 *>(ar + kChainPlane + 4 * g);
         a.lo.v = *reinterpret_cast<const bf16x8 *>(ar + 2 * kChainPlane + 4 * g);
 #pragma unroll
         for (int cbl = 0; cbl < 2; ++cbl) {
-          const unsigned char *bq = pb + gl * 12288 + (2 * ch + cbl) * 1024 + lane * 16;
+          const unsigned char *bq = pb + gl * kChainGroupBytes + (2 * ch + cbl) * 1024 + lane * 16;
           Split8 b;
           b.hi.v = *reinterpret_cast<const bf16x8 *>(bq);
           b.mid.v = *reinterpret_cast<const bf16x8 *>(bq + 4096);
@@ -187,10 +215,12 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
           acc[cbl] = mfma_x6(a, b, acc[cbl]);
         }
       }
+      __builtin_amdgcn_sched_barrier(0);                      // (the wait for the chunk stays behind the step's MFMAs)
       uint4 *pw = reinterpret_cast<uint4 *>(Pb + ((cc + 1) & 1) * kChainChunkBytes);
 #pragma unroll
-      for (int i = 0; i < 3; ++i) pw[i * kChainThreads + t] = pc[i];
+      for (int i = 0; i < 3; ++i) pw[i * kChainThreads + t] = pc[(cc + 1) & 1][i];
       lds_barrier();
+      __builtin_amdgcn_sched_barrier(0);
     }
   };
   int rid[16];                                                // the ids of this lane's 16 accumulator rows
@@ -220,7 +250,7 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
   };
   float colsum[2] = {0.f, 0.f};                               // backward: this lane's two columns of dPn
 
-  // ---- prologue: the first pass's ids, then its rows; the first quarter panel beside them
+  // ---- prologue: the first pass's ids, then its rows; the first two chunks of the panels beside them (LDS, register set 1)
   load_ids(lo);
   load_rows(rs_A0);
   {
@@ -230,8 +260,9 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
       const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_pan, (i * kChainThreads + t) * 16, 0, 0);
       pw[i * kChainThreads + t] = make_uint4(v.x, v.y, v.z, v.w);
     }
+    request(1, 1);
   }
-  for (int g0 = lo; g0 < hi; g0 += 4) {
+  for (int g0 = lo; g0 < hi; g0 += kChainTiles) {
     stage(true);
     lds_barrier();
 #pragma unroll
@@ -248,7 +279,7 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
       load_rows(rs_A2);                                       // S_out
       product(3);                                             // + S_in Bn_in
       stage(false); lds_barrier();
-      load_ids(g0 + 4);                                       // the next pass
+      load_ids(g0 + kChainTiles);                                       // the next pass
       product(4);                                             // + S_out Bn_out
       load_rows(rs_A0);                                       // the next pass's x: requested ahead of this epilogue's stores
 #pragma unroll
@@ -281,7 +312,7 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
         for (int r = 0; r < 16; ++r) hv[cb][r] = sbuf_load1(rs_X, rid[r], (uint32_t)(64 * ch + 32 * cb + li) * 4u);
       zero_acc(); product(0);                                 // dxn W2
       if (full) load_rows(rs_A1);                             // dP_dst: requested ahead of the stores
-      else load_ids(g0 + 4);
+      else load_ids(g0 + kChainTiles);
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -302,7 +333,7 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
         load_rows(rs_A2);                                     // dP_src
         product(4);                                           // + dP_dst Wx1^T
         stage(false); lds_barrier();
-        load_ids(g0 + 4);
+        load_ids(g0 + kChainTiles);
         float res[2][16];
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
@@ -319,9 +350,9 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
     }
   }
   if (BWD) {
-    // column sums: the two half-waves of a lane's column, then the four tile waves / the 16 staging rows through LDS, in order
+    // column sums: the two half-waves of a lane's column, then the tiles' waves / the staging rows through LDS, in order
     float *red = reinterpret_cast<float *>(Pb);
-    float *redA = red + 4 * 128;
+    float *redA = red + kChainTiles * 128;
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
       const float s = colsum[cb] + __shfl_xor(colsum[cb], 32, 64);
@@ -332,19 +363,19 @@ __global__ __launch_bounds__(kChainThreads) void node_chain_k(ChainArgs p) {
     if (t < 128) {
       float s = red[t];
 #pragma unroll
-      for (int w = 1; w < 4; ++w) s += red[w * 128 + t];
+      for (int w = 1; w < kChainTiles; ++w) s += red[w * 128 + t];
       p.partial[(int64_t)blockIdx.x * 128 + t] = s;
       float sa = redA[t];
 #pragma unroll
-      for (int w = 1; w < 16; ++w) sa += redA[w * 128 + t];
+      for (int w = 1; w < kChainStageRows; ++w) sa += redA[w * 128 + t];
       p.partialA[(int64_t)blockIdx.x * 128 + t] = sa;
     }
   }
 }
 
 inline unsigned chain_blocks(int64_t tiles_bound) {
-  const int64_t want = (tiles_bound + 3) / 4;
-  return (unsigned)(want < 1 ? 1 : (want > 256 ? 256 : want));
+  const int64_t want = (tiles_bound + kChainTiles - 1) / kChainTiles;
+  return (unsigned)(want < 1 ? 1 : (want > kChainMaxBlocks ? kChainMaxBlocks : want));
 }
 
 constexpr int kMaxDevicesC = 64;

@@ -1230,8 +1230,8 @@ int dmp_bwd_h1_w(const float *dO, int64_t ldo, const float *W2, int64_t ldw, con
 
 /*
  * The node side of a layer over the kept nodes' tiles (dmp_kept_rows(tiles = 1)) as ONE launch per pass (csrc/dmp_nodechain.hip;
- * SubgraphCountingMatching/models/dmpnn.py:113,121,125,129-140 over the folded weights): the rows stay in a 512-thread workgroup
- * (128 rows at a time: operand as bf16 pieces in LDS, the [128, 128] result block in registers), the six weight panels stream
+ * SubgraphCountingMatching/models/dmpnn.py:113,121,125,129-140 over the folded weights): the rows stay in a 256-thread workgroup, two per CU
+ * (64 rows at a time: operand as bf16 pieces in LDS, the [64, 128] result block in registers), the six weight panels stream
  * through LDS -- what dmp_out_fwd_typed / dmp_bwd_h1_typed do as three dependent launches with partial sums through memory.
  *   dmp_node_chain_pack   the panels as bf16 pieces in fragment order, once per step: panel j is B[k][c] = W[k * ld + c], or with
  *                         `transposed` W[c * ld + k]; out [num_panels * dmp_node_chain_panel_words()] (num_panels <= 12)
