@@ -328,6 +328,9 @@ SIGNATURES = {
     "dmp_bwd_h1_w_blocks": (c_i64, [c_i64]),
     "dmp_bwd_h1_w": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64,
                              c_ptr, c_ptr, c_ptr, c_ptr]),
+    "dmp_bwd_h1_w_max_codes": (c_int, []),
+    "dmp_bwd_h1_w_codes": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_i64,
+                                   c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr]),
     "dmp_node_chain_blocks": (c_i64, [c_i64]),
     "dmp_node_chain_panel_words": (c_i64, []),
     "dmp_node_chain_pack": (c_int, [_p(dmp_chain_panel), c_int, c_ptr, c_ptr]),

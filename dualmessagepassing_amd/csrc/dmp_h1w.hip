@@ -64,7 +64,37 @@ typedef __attribute__((address_space(3))) v4s *lds_v4s_ptr;
 // chunk swizzle of the image: 16-byte chunk ch (0..15) of row `row` lives at 256 row + 16 (ch ^ swz(row))
 __device__ __forceinline__ uint32_t swz(uint32_t row) { return ((row & 3u) << 2) | ((row >> 2) & 3u); }
 
-__global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const H1WArgs p) {
+// ---- the first layer's variant (dmp_bwd_h1_w_codes): the layer's input rows are z = enc W0 (label codes, K <= 16 columns), so its
+// weight gradient needs  XX = [enc^T dPre | (c (.) enc)^T dPre | enc^T dO]  over the SAME rows -- dO is this kernel's LDS image and
+// dPre is in the row waves' registers.  The codes go in as ONE 32-row A operand  A = [enc | c (.) enc]^T  (rows 0-15 / 16-31; rows
+// >= K are zeros), staged per tile by the column waves' 256 threads as bf16 pieces in its own small image ([32 m][32 tile rows],
+// 64-byte rows, three buffers: a tile's codes are read in its step and in the step after, while the tile after that is staged).
+// Column wave j keeps both products of the columns 32 j .. (the row waves have no registers to spare: with 16 more in their loop the
+// W2 panel spilled):
+//   A dO[:, 32 j ..]     in the tile's step, from the dO image through the transposed read, 12 MFMAs per tile (the lower half of the
+//                        result, (c enc)^T dO, is not needed and not stored); only with RES;
+//   A dPre[:, 32 j ..]   one step later: row wave j writes its 32 x 32 block of dPre as a bf16-piece image (64-byte rows) in its epilogue
+//                        -- which runs behind the tile's barrier -- and both roles meet at a SECOND barrier per tile, the column waves
+//                        after kXBlock + 1 of their eight blocks; 12 MFMAs per tile: blocks one and two of XX at once.
+// Rows outside the table's edge range [r0, r1) -- and padding slots -- read zero codes through descriptors that cover the range alone.
+struct H1WCodeArgs : H1WArgs {
+  const float *enc; uint32_t lde4;       // code rows of the range: enc[r0 ..], row stride in bytes
+  const float *coef;                     // coef_e[r0 ..]
+  uint32_t enc_bytes;                    // ((r1 - r0 - 1) lde + K) 4, or 0 for an empty range
+  int r0, nrange, K;
+  float *partialX;                       // [gridDim.x, K * (RES ? 3 : 2) * 128]
+};
+constexpr int kXImgB = 4 * 3 * 32 * 64;              // the row waves' dPre images (one per wave): 4 x (3 planes x 32 rows x 64 bytes) = 24576
+constexpr int kCodeBufB = 3 * 32 * 64;               // one tile's code image: 3 planes x 32 m x 64 bytes
+constexpr int kXBlock = 1;                           // the column waves' block after which they meet the row waves' second barrier
+constexpr int kH1WCodesLdsBytes = kH1WLdsBytes + kXImgB + 3 * kCodeBufB;   // 160128 of 163840
+
+// MODE 0: the plain kernel (H1WArgs); 1: + blocks one and two of XX; 2: + the third block (H1WCodeArgs)
+template <int MODE>
+__global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const std::conditional_t<MODE == 0, H1WArgs, H1WCodeArgs> p) {
+  constexpr bool CODES = MODE > 0, RES = MODE == 2;
+  constexpr int kXOff = kH1WLdsBytes, kCodeOff = kH1WLdsBytes + kXImgB;
+  constexpr uint32_t kOOB = 0xFFFFF000u;
   extern __shared__ __attribute__((aligned(256))) unsigned char lds[];
   float *const scr_all = reinterpret_cast<float *>(lds + kImgB);
   uint32_t *const rowC = reinterpret_cast<uint32_t *>(lds + kImgB + kScrB);     // [3][32]: store row of every slot (-1: none)
@@ -118,6 +148,60 @@ __global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const H1WArgs p) {
   auto stage_scalars = [&](int par) {                   // store row of every slot of the staged tile (row waves' threads < 32)
     if (!cols && u < kSub) rowC[par * kSub + u] = own_staged >= 0 ? (uint32_t)own_staged : kNone;
   };
+  // ---- CODES: the code image, staged by the column waves' threads on the schedule of their rows (ids three tiles ahead, values
+  // two, the image one): thread u owns code column cm = u % 16 of the tile's rows 2 rp, 2 rp + 1 (rp = u / 16) -- a packed pair of
+  // bf16 per piece.  Chunk swizzle: the 16-byte chunk c of m's 64-byte row lives at 16 (c ^ (m / 4) % 4) (the fragment read is a
+  // ds_read_b128 per lane, 32 lanes 64 bytes apart).
+  const int rp = u >> 4, cm = u & 15;
+  int cid0 = -1, cid1 = -1, cid_tile = 0;
+  float ce0 = 0.f, ce1 = 0.f, cc0 = 0.f, cc1 = 0.f;
+  // (the id loads are unconditional, at the range's last tile for a tile past its end, and "no row" is selected where the ids are
+  // consumed: a load whose only use sits under a wave-uniform condition is sunk under a branch with a full wait behind it, (oo))
+  [[maybe_unused]] auto load_cids = [&](int k) {
+    if constexpr (CODES) {
+      const uint32_t so = (uint32_t)(lo + (k < mine ? k : mine - 1)) * (kSub * 4u);
+      cid0 = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_slot, (2 * rp) * 4, (int)so, 0);
+      cid1 = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_slot, (2 * rp + 1) * 4, (int)so, 0);
+      cid_tile = k;
+    }
+  };
+  [[maybe_unused]] auto load_codes = [&]() {             // (a slot outside the range, a padding slot: beyond the descriptors -> zeros)
+    if constexpr (CODES) {
+      const rsrc_t rs_enc = make_rsrc(p.enc, p.enc_bytes);
+      const rsrc_t rs_coef = make_rsrc(p.coef, (uint32_t)p.nrange * 4u);
+      const uint32_t cmo = (uint32_t)(cm < p.K ? cm : p.K - 1) * 4u;
+      const uint32_t i0 = (uint32_t)(cid0 - p.r0), i1 = (uint32_t)(cid1 - p.r0);
+      const bool live = cid_tile < mine;
+      const bool in0 = live && i0 < (uint32_t)p.nrange, in1 = live && i1 < (uint32_t)p.nrange;
+      ce0 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_enc, (int)(in0 ? i0 * p.lde4 + cmo : kOOB), 0, 0));
+      ce1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_enc, (int)(in1 ? i1 * p.lde4 + cmo : kOOB), 0, 0));
+      cc0 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_coef, (int)(in0 ? i0 * 4u : kOOB), 0, 0));
+      cc1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_coef, (int)(in1 ? i1 * 4u : kOOB), 0, 0));
+    }
+  };
+  [[maybe_unused]] auto stage_codes = [&](int cbuf) {
+    if constexpr (CODES) {
+      const float a0 = cm < p.K ? ce0 : 0.f, a1 = cm < p.K ? ce1 : 0.f;
+      uint32_t ph, pm, pl;
+      split_pair(a0, a1, ph, pm, pl);
+      const uint32_t off = (uint32_t)(kCodeOff + cbuf * kCodeBufB + 64 * cm) + 16u * ((uint32_t)(rp >> 2) ^ (uint32_t)((cm >> 2) & 3)) + 4u * (uint32_t)(rp & 3);
+      *reinterpret_cast<uint32_t *>(lds + off) = ph;
+      *reinterpret_cast<uint32_t *>(lds + off + 2048) = pm;
+      *reinterpret_cast<uint32_t *>(lds + off + 4096) = pl;
+      split_pair(cc0 * a0, cc1 * a1, ph, pm, pl);       // m = 16 + cm: the same swizzle ((m / 4) % 4 is unchanged)
+      *reinterpret_cast<uint32_t *>(lds + off + 1024) = ph;
+      *reinterpret_cast<uint32_t *>(lds + off + 1024 + 2048) = pm;
+      *reinterpret_cast<uint32_t *>(lds + off + 1024 + 4096) = pl;
+    }
+  };
+  // the A operand's fragment: lane (li, h) holds m = li, tile rows 16 kg + 8 h .. + 7 = chunk 2 kg + h of m's row
+  const uint32_t ca0 = 64u * (uint32_t)li + 16u * ((uint32_t)h ^ (uint32_t)((li >> 2) & 3));
+  [[maybe_unused]] auto code_frag = [&](int cbuf, int kg, Split8 &s) {
+    const unsigned char *b = lds + kCodeOff + cbuf * kCodeBufB + (ca0 ^ (uint32_t)(32 * kg));
+    s.hi.v = *reinterpret_cast<const bf16x8 *>(b);
+    s.mid.v = *reinterpret_cast<const bf16x8 *>(b + 2048);
+    s.lo.v = *reinterpret_cast<const bf16x8 *>(b + 4096);
+  };
 
   // ======================================================================== the row product (waves 0-3)
   const int cs = wave & 3;
@@ -156,6 +240,8 @@ __global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const H1WArgs p) {
     hs[k] = *reinterpret_cast<const uint2 *>(lds + kOpB + (uint32_t)buf * kBufB + 256u * rr + 16u * (ch ^ swz(rr)) + 8u * (uint32_t)(lane & 1));
   };
   f32x16 acc;
+  // CODES: transposed read of a 32-column block of the dPre image (64-byte rows): as tr_base below, row 8 (G >> 1) + q, columns 16 (G & 1) + 4 pp ..
+  const uint32_t xt0 = 64u * (uint32_t)(8 * (lane >> 5) + ((lane & 15) >> 2)) + 32u * (uint32_t)((lane >> 4) & 1) + 8u * (uint32_t)(lane & 3);
   float4 colsum = make_float4(0.f, 0.f, 0.f, 0.f);
   // one tile of the row product: 8 k-groups x 6 piece MFMAs with, in their shadow, the sign reads of this tile (groups 0-1),
   // the staging of tile k+1 (2-4), the row requests of tile k+2 (4-6) and the id requests of tile k+3 (7)
@@ -213,6 +299,15 @@ __global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const H1WArgs p) {
       v.z = act_bwd(__uint_as_float(hs[k].y << 16), v.z, slope); v.w = act_bwd(__uint_as_float(hs[k].y & 0xFFFF0000u), v.w, slope);
       colsum.x += v.x; colsum.y += v.y; colsum.z += v.z; colsum.w += v.w;
       sbuf_store4(v, rs_C, (int)rowC[par * kSub + rr], col4);
+      if constexpr (CODES) {                               // the image of this wave's 32 x 32 block of dPre: row rr, columns 4 (lane & 7) ..
+        uint2 ph, pm, pl;
+        split_pair(v.x, v.y, ph.x, pm.x, pl.x);
+        split_pair(v.z, v.w, ph.y, pm.y, pl.y);
+        unsigned char *xi = lds + kXOff + cs * (3 * 2048) + 64 * rr + 8 * (lane & 7);
+        *reinterpret_cast<uint2 *>(xi) = ph;
+        *reinterpret_cast<uint2 *>(xi + 2048) = pm;
+        *reinterpret_cast<uint2 *>(xi + 4096) = pl;
+      }
     }
   };
 
@@ -245,7 +340,32 @@ __global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const H1WArgs p) {
   };
   // one tile of the column product: 2 k-groups x (2 x 2) blocks x 6 piece MFMAs; in their shadow the staging of tile k+1's H1 rows,
   // the row requests of tile k+2 and the id requests of tile k+3
-  auto cols_step = [&](int k, f32x16 (&wacc)[2][2]) {
+  // CODES: column wave j = wave % 4 also forms  [enc | c enc]^T dO[:, 32 j ..]  (RES; cur3 = k % 3: the tile's code buffer), and the
+  // column waves' threads stage the code image of tile k+1 (nxt3), request the codes of tile k+2 and the slot ids of tile k+3
+  const uint32_t tX = tr_base((wave >> 1) & 1);
+  const int xblk = wave & 1;
+  f32x16 xaccP, xaccO;                                   // [enc | c enc]^T dPre[:, 32 j ..] and ... ^T dO[:, 32 j ..]
+  // the dPre product of the tile BEFORE (its image is complete behind the row waves' second barrier; its codes: buffer prv3)
+  auto xprod = [&](int prv3) {
+    Split8 a[2], b[2];
+#pragma unroll
+    for (int kg = 0; kg < 2; ++kg) {
+      code_frag(prv3, kg, a[kg]);
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) {
+        Frag8 &f = pl == 0 ? b[kg].hi : pl == 1 ? b[kg].mid : b[kg].lo;
+        const unsigned char *xb = lds + kXOff + (wave & 3) * (3 * 2048) + pl * 2048 + xt0 + 1024 * kg;
+        const v4s x = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_ptr)(xb));
+        const v4s y = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_ptr)(xb + 256));
+        f.v = __builtin_shufflevector(x, y, 0, 1, 2, 3, 4, 5, 6, 7);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    xaccP = mfma_x6(a[0], b[0], xaccP);
+    xaccP = mfma_x6(a[1], b[1], xaccP);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto cols_step = [&](int k, f32x16 (&wacc)[2][2], int cur3, int nxt3, int prv3) {
     const int buf = k & 1;
     int act = 0;
     // eight blocks (kg, jb, ib); the fragments the next block needs are requested BEFORE this block's MFMAs
@@ -260,18 +380,38 @@ __global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const H1WArgs p) {
         tr_split(tB, buf, jb ^ 1, jb == 1 ? kg + 1 : kg, nfb);
         if (b == 3) { tr_split(tA, buf, 0, 1, nfa[0]); tr_split(tA, buf, 1, 1, nfa[1]); }
       }
+      if constexpr (RES) {
+        if (b == 7) { code_frag(cur3, 0, nfa[0]); tr_split(tX, buf, xblk, 0, nfb); }       // (the spare fragment registers of the last block)
+      }
       __builtin_amdgcn_sched_barrier(0);
       wacc[ib][jb] = mfma_x6(fa[ib], fb, wacc[ib][jb]);
       __builtin_amdgcn_sched_barrier(0);
       if (act < 4) stage_row(buf ^ 1, act);
       else load_row(act - 4);
       ++act;
+      if constexpr (CODES) {
+        if (b == 3) stage_codes(nxt3);
+        if (b == 7) load_codes();
+        if (b == kXBlock && k > 0) {   // (uniform over the workgroup) the row waves have written tile k-1's dPre image: their second barrier
+          lds_barrier();
+          xprod(prv3);
+        }
+      }
       if (ib == 1 && b + 1 < 8) {
         fb = nfb;
         if (b == 3) { fa[0] = nfa[0]; fa[1] = nfa[1]; }
       }
     }
+    if constexpr (RES) {
+      code_frag(cur3, 1, fa[0]);
+      tr_split(tX, buf, xblk, 1, fb);
+      __builtin_amdgcn_sched_barrier(0);
+      xaccO = mfma_x6(nfa[0], nfb, xaccO);
+      xaccO = mfma_x6(fa[0], fb, xaccO);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     load_ids(k + 3);
+    load_cids(k + 3);
   };
 
   // ======================================================================== the loop (both roles: one barrier per tile)
@@ -282,11 +422,23 @@ __global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const H1WArgs p) {
     }
     float4 *pw4 = reinterpret_cast<float4 *>(p.partialW + (int64_t)blockIdx.x * (kHW * kHW));
     for (int m = threadIdx.x; m < kHW * kHW / 4; m += kThreadsW) pw4[m] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (CODES) {
+      const int nx = p.K * (RES ? 3 : 2) * kHW;
+      float *px = p.partialX + (int64_t)blockIdx.x * nx;
+      for (int m = threadIdx.x; m < nx; m += kThreadsW) px[m] = 0.f;
+    }
     return;
   }
-  load_ids(0);
-  load_rows();                 // tile 0
-  load_ids(1);
+  if constexpr (CODES) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { xaccP[r] = 0.f; xaccO[r] = 0.f; }
+  }
+  auto start_rows = [&]() {
+    load_ids(0);
+    load_rows();               // tile 0
+    load_ids(1);
+  };
+  if constexpr (!CODES) start_rows();      // (CODES: inside each role's branch -- tile 0's rows are then live in one role's code only)
   // The two roles run their own loops (same number of barriers): nothing of one role's register state -- the panel's 96
   // registers, the quadrant's 64 accumulators -- is live in the other's code.
   float *tot = reinterpret_cast<float *>(lds);   // after the loop the image is free: the [128, 128] total goes through it for 16-byte stores
@@ -298,14 +450,40 @@ __global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const H1WArgs p) {
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) wacc[i][j][r] = 0.f;
+    if constexpr (CODES) start_rows();
 #pragma unroll
     for (int m = 0; m < kSubLoads; ++m) stage_row(0, m);
+    if constexpr (CODES) {     // the code image's pipeline, started like the rows'
+      load_cids(0);
+      load_codes();            // tile 0
+      load_cids(1);
+      stage_codes(0);
+    }
     load_rows();               // tile 1
+    load_codes();
     load_ids(2);
+    load_cids(2);
     lds_barrier();
+    int cur3 = 0, prv3 = 2;
     for (int k = 0; k < mine; ++k) {
-      cols_step(k, wacc);
+      const int nxt3 = cur3 == 2 ? 0 : cur3 + 1;
+      cols_step(k, wacc, cur3, nxt3, prv3);
+      prv3 = cur3;
+      cur3 = nxt3;
       lds_barrier();           // tile k+1 is staged for everyone, everyone is done with tile k's image
+    }
+    if constexpr (CODES) {
+      lds_barrier();           // the last tile's dPre image
+      xprod(prv3);
+      // XX's blocks of this wave's 32 columns: accumulator row m < 16 -> block one (P) / three (O), m >= 16 -> block two (P)
+      constexpr int nb = RES ? 3 : 2;
+      float *px = p.partialX + (int64_t)blockIdx.x * (p.K * nb * kHW) + 32 * (wave & 3) + li;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = (r & 3) + 8 * (r >> 2) + 4 * h, kk = m & 15;
+        if (kk < p.K) px[(kk * nb + (m >> 4)) * kHW] = xaccP[r];
+        if (RES && r < 8 && kk < p.K) px[(kk * nb + 2) * kHW] = xaccO[r];
+      }
     }
     __syncthreads();
 #pragma unroll
@@ -316,6 +494,7 @@ __global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const H1WArgs p) {
         for (int r = 0; r < 16; ++r)
           tot[(64 * pw + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h) * kHW + 64 * qw + 32 * j + li] = wacc[i][j][r];
   } else {
+    if constexpr (CODES) start_rows();
     load_panel();              // (requested behind tile 0's rows: the two round trips run side by side)
 #pragma unroll
     for (int m = 0; m < kSubLoads; ++m) stage_row(0, m);
@@ -328,6 +507,7 @@ __global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const H1WArgs p) {
       rows_step(k, par3);
       lds_barrier();
       rows_epilogue(par3);
+      if constexpr (CODES) lds_barrier();                  // tile k's dPre image is complete: the column waves' product reads it
       par3 = par3 == 2 ? 0 : par3 + 1;
     }
     __syncthreads();
@@ -969,15 +1149,28 @@ inline unsigned h1w_blocks(int64_t tiles_bound) {
 }
 
 constexpr int kMaxDevicesW = 64;
+template <int MODE>
 inline bool h1w_lds_ready() {
   static bool done[kMaxDevicesW] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesW) dev = 0;
   if (done[dev]) return true;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&h1w_k), hipFuncAttributeMaxDynamicSharedMemorySize, kH1WLdsBytes);
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&h1w_k<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           MODE == 0 ? kH1WLdsBytes : kH1WCodesLdsBytes);
   if (e != hipSuccess) { set_last_hip_error(e); return false; }
   done[dev] = true;
   return true;
+}
+
+// dmp_bwd_h1_w's argument checks (both entries); DMP_OK: launch
+inline int h1w_check(const float *dO, int64_t ldo, const float *W2, int64_t ldw, const float *H1, int64_t ldh, const int32_t *slot_edge,
+                     const int32_t *num_tiles, int64_t tiles_bound, int64_t E, int H, float *dPre, int64_t ldg) {
+  if (!dO || !W2 || !H1 || !dPre || !slot_edge || !num_tiles || ldo < H || ldw < H || ldh < H || ldg < H) return DMP_ERR_BAD_ARG;
+  if (ldo % 4 || ldh % 4 || ldg % 4 || !aligned16(dO) || !aligned16(H1) || !aligned16(dPre)) return DMP_ERR_UNSUPPORTED;
+  if (!stride_ok(ldo) || !stride_ok(ldh) || !stride_ok(ldg) || E >= ((int64_t)1 << 30) || tiles_bound * kSub * 4 >= ((int64_t)1 << 32) - 8192 ||
+      (int64_t)H * ldw * 4 >= ((int64_t)1 << 32) - 8192 || !fits4g(E, ldo) || !fits4g(E, ldh) || !fits4g(E, ldg))
+    return DMP_ERR_UNSUPPORTED;                           // (arrays of 4 GiB and more: the two-launch form has the 64-bit row kernels)
+  return DMP_OK;
 }
 
 }  // namespace
@@ -1004,16 +1197,54 @@ int dmp_bwd_h1_w(const float *dO, int64_t ldo, const float *W2, int64_t ldw, con
     if (hipMemsetAsync(partial_w, 0, sizeof(float) * H * H * rows, st) != hipSuccess) return DMP_ERR_HIP;
     return DMP_OK;
   }
-  if (!dO || !W2 || !H1 || !dPre || !slot_edge || !num_tiles || ldo < H || ldw < H || ldh < H || ldg < H) return DMP_ERR_BAD_ARG;
-  if (ldo % 4 || ldh % 4 || ldg % 4 || !aligned16(dO) || !aligned16(H1) || !aligned16(dPre)) return DMP_ERR_UNSUPPORTED;
-  if (!stride_ok(ldo) || !stride_ok(ldh) || !stride_ok(ldg) || E >= ((int64_t)1 << 30) || tiles_bound * kSub * 4 >= ((int64_t)1 << 32) - 8192 ||
-      (int64_t)H * ldw * 4 >= ((int64_t)1 << 32) - 8192 || !fits4g(E, ldo) || !fits4g(E, ldh) || !fits4g(E, ldg))
-    return DMP_ERR_UNSUPPORTED;                           // (arrays of 4 GiB and more: the two-launch form has the 64-bit row kernels)
-  if (!h1w_lds_ready()) return DMP_ERR_HIP;
+  if (const int rc = h1w_check(dO, ldo, W2, ldw, H1, ldh, slot_edge, num_tiles, tiles_bound, E, H, dPre, ldg)) return rc;
+  if (!h1w_lds_ready<0>()) return DMP_ERR_HIP;
   H1WArgs a{};
   a.dO = dO; a.ldo = ldo; a.H1 = H1; a.ldh = ldh; a.W2 = W2; a.ldw = ldw; a.dPre = dPre; a.ldg = ldg; a.E = E;
   a.slot_edge = slot_edge; a.num_tiles = num_tiles; a.slope = slope; a.partial = partial; a.partialA = partial_rows; a.partialW = partial_w;
-  h1w_k<<<h1w_blocks(tiles_bound), kThreadsW, kH1WLdsBytes, st>>>(a);
+  h1w_k<0><<<h1w_blocks(tiles_bound), kThreadsW, kH1WLdsBytes, st>>>(a);
+  return check_launch();
+}
+
+int dmp_bwd_h1_w_max_codes(void) { return 16; }
+
+int dmp_bwd_h1_w_codes(const float *dO, int64_t ldo, const float *W2, int64_t ldw, const float *H1, int64_t ldh,
+                       const int32_t *slot_edge, const int32_t *num_tiles, int64_t tiles_bound, int64_t E, int H, float slope,
+                       float *dPre, int64_t ldg, float *partial, float *partial_rows, float *partial_w,
+                       const float *enc, int64_t lde, int K, const float *coef_e, int64_t r0, int64_t r1, int residual,
+                       float *partial_x, void *stream) {
+  if (H != 128 || g_exact_fp32 || K > 16) return DMP_ERR_UNSUPPORTED;
+  if (E < 0 || tiles_bound < 0 || K < 1 || lde < K || r0 < 0 || r1 < r0 || r1 > E) return DMP_ERR_BAD_ARG;
+  if (!partial || !partial_w || !partial_x || !aligned16(partial) || !aligned16(partial_w) || (partial_rows && !aligned16(partial_rows)))
+    return DMP_ERR_BAD_ARG;
+  if (!slope_ok(slope)) return DMP_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = residual ? 3 : 2;
+  if (E == 0) {
+    const size_t rows = (size_t)h1w_blocks(tiles_bound);
+    if (hipMemsetAsync(partial, 0, sizeof(float) * H * rows, st) != hipSuccess) return DMP_ERR_HIP;
+    if (partial_rows && hipMemsetAsync(partial_rows, 0, sizeof(float) * H * rows, st) != hipSuccess) return DMP_ERR_HIP;
+    if (hipMemsetAsync(partial_w, 0, sizeof(float) * H * H * rows, st) != hipSuccess) return DMP_ERR_HIP;
+    if (hipMemsetAsync(partial_x, 0, sizeof(float) * K * nb * H * rows, st) != hipSuccess) return DMP_ERR_HIP;
+    return DMP_OK;
+  }
+  if (const int rc = h1w_check(dO, ldo, W2, ldw, H1, ldh, slot_edge, num_tiles, tiles_bound, E, H, dPre, ldg)) return rc;
+  if (r1 > r0 && (!enc || !coef_e)) return DMP_ERR_BAD_ARG;
+  if (!fits4g(r1 - r0, lde)) return DMP_ERR_UNSUPPORTED;      // (the code rows' raw descriptor: byte offsets in 32 bits)
+  H1WCodeArgs a{};
+  a.dO = dO; a.ldo = ldo; a.H1 = H1; a.ldh = ldh; a.W2 = W2; a.ldw = ldw; a.dPre = dPre; a.ldg = ldg; a.E = E;
+  a.slot_edge = slot_edge; a.num_tiles = num_tiles; a.slope = slope; a.partial = partial; a.partialA = partial_rows; a.partialW = partial_w;
+  const int64_t n = r1 - r0;
+  a.enc = n > 0 ? enc + r0 * lde : nullptr; a.lde4 = (uint32_t)(lde * 4); a.coef = n > 0 ? coef_e + r0 : nullptr;
+  a.enc_bytes = n > 0 ? (uint32_t)(((n - 1) * lde + K) * 4) : 0u;
+  a.r0 = (int)r0; a.nrange = (int)n; a.K = K; a.partialX = partial_x;
+  if (residual) {
+    if (!h1w_lds_ready<2>()) return DMP_ERR_HIP;
+    h1w_k<2><<<h1w_blocks(tiles_bound), kThreadsW, kH1WCodesLdsBytes, st>>>(a);
+  } else {
+    if (!h1w_lds_ready<1>()) return DMP_ERR_HIP;
+    h1w_k<1><<<h1w_blocks(tiles_bound), kThreadsW, kH1WCodesLdsBytes, st>>>(a);
+  }
   return check_launch();
 }
 

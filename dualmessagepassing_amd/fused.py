@@ -945,9 +945,31 @@ def h1w_ok(d_o, h1, H):
             and h1.size(0) * h1.stride(0) * 4 < (1 << 32) - 65536 and d_o.size(0) * H * 4 < (1 << 32) - 65536)
 
 
-def bwd_h1_w(d_o, W2, h1, tiles, slope=0.0, out=None):
+USE_H1W_CODES = True      # the first layer's code weight gradient of the target table from ``bwd_h1_w``'s launch (csrc/dmp_h1w.hip) instead of ``l0_bwd_w``'s
+H1W_MAX_CODES = 16        # ``dmp_bwd_h1_w_max_codes()``: one 16-row half of the 32-row code operand
+
+
+def h1w_codes_ok(l0, tables, walked, h1w=True):
+    """``bwd_h1_w(codes=...)`` takes over the LAST embedding table's ``l0_bwd_w`` launch: the layer is the first one (``l0``: its
+    ``Layer0Codes``), the one-launch kernel runs (``h1w``: ``h1w_ok`` -- H = 128, bf16x6, arrays below 4 GiB), at most
+    ``H1W_MAX_CODES`` fp32 code columns with unit stride, two tables or more (the pattern's rows keep their ``l0_bwd_w`` launch) of
+    which the last has edge rows, and ``l0_bwd_w`` would have walked the rows of the tile list that lie in the table's range --
+    ``walked``: "kept" (the list holds the rows a 0 / 1 gate keeps, and ``l0_bwd_w`` walks the gate's mask over the range) or "all"
+    (the identity list of a step without a gate: ``l0_bwd_w`` leaves out at most rows whose codes are zeros, which add zeros)."""
+    if not (USE_H1W_CODES and l0 is not None and h1w and walked in ("kept", "all")):
+        return False
+    enc = l0.enc
+    return bool(1 <= l0.K <= H1W_MAX_CODES and len(tables) >= 2 and tables[-1][1][1] > tables[-1][1][0]
+                and enc.dtype == torch.float32 and enc.dim() == 2 and enc.stride(1) == 1 and enc.size(1) >= l0.K
+                and enc.size(0) * enc.stride(0) * 4 < (1 << 32) - 65536)
+
+
+def bwd_h1_w(d_o, W2, h1, tiles, slope=0.0, out=None, codes=None):
     """``(dPre, column sums of dPre, column sums of the kept rows of d_o, d_o^T h1)`` over the rows of ``tiles``: what
-    ``bwd_h1_typed`` and ``atb_typed(d_o, h1, plain=True)`` return, from one pass over the two operands (``dmp_bwd_h1_w``)."""
+    ``bwd_h1_typed`` and ``atb_typed(d_o, h1, plain=True)`` return, from one pass over the two operands (``dmp_bwd_h1_w``).
+    ``codes = dict(enc, K, coef_e, rows=(r0, r1), residual[, out])``: the first layer's launch (``dmp_bwd_h1_w_codes``) -- a fifth
+    value ``[enc^T dPre | (coef_e enc)^T dPre (| enc^T d_o)]``, [K, 2H or 3H], over the rows of ``tiles`` inside ``rows``: what
+    ``l0_bwd_w`` makes from a second read of ``dPre`` and ``d_o`` (``out``: where the reduced block goes)."""
     lib = _lib.load()
     E, H = d_o.shape
     slot_edge, _, num_tiles, bound = tiles
@@ -957,6 +979,21 @@ def bwd_h1_w(d_o, W2, h1, tiles, slope=0.0, out=None):
     part_rows = torch.empty_like(part)
     part_w = torch.empty((G, H * H), dtype=torch.float32, device=d_o.device)
     W2 = W2.contiguous()
+    if codes is not None:
+        enc, K, coef_e, (r0, r1), residual = codes["enc"], int(codes["K"]), codes["coef_e"], codes["rows"], bool(codes["residual"])
+        _lib.require_gpu(enc, coef_e)
+        if enc.dtype != torch.float32 or enc.stride(1) != 1 or coef_e.dtype != torch.float32 or not coef_e.is_contiguous() or coef_e.numel() < E:
+            raise _lib.DmpError("bwd_h1_w: codes need fp32 code rows of unit column stride and one fp32 coefficient per edge row")
+        nb = 3 if residual else 2
+        part_x = torch.empty((G, K * nb * H), dtype=torch.float32, device=d_o.device)
+        with _lib.timed("bwd_h1_w[H=%d,E=%d]", (H, E), 12 * H * E + 4 * E):
+            check(lib.dmp_bwd_h1_w_codes(ptr(d_o), d_o.stride(0), ptr(W2), W2.size(1), ptr(h1), h1.stride(0), ptr(slot_edge), ptr(num_tiles),
+                                         bound, E, H, slope, ptr(d_g), d_g.stride(0), ptr(part), ptr(part_rows), ptr(part_w),
+                                         ptr(enc), enc.stride(0), K, ptr(coef_e), int(r0), int(r1), int(residual), ptr(part_x), stream_ptr()),
+                  "dmp_bwd_h1_w_codes")
+        xo = codes.get("out")
+        xx = reduce_partials(part_x, None if xo is None else xo.view(-1)).view(K, nb * H)
+        return d_g, reduce_partials(part), reduce_partials(part_rows), reduce_partials(part_w).view(H, H), xx
     with _lib.timed("bwd_h1_w[H=%d,E=%d]", (H, E), 12 * H * E + 4 * E):
         check(lib.dmp_bwd_h1_w(ptr(d_o), d_o.stride(0), ptr(W2), W2.size(1), ptr(h1), h1.stride(0), ptr(slot_edge), ptr(num_tiles), bound,
                                E, H, slope, ptr(d_g), d_g.stride(0), ptr(part), ptr(part_rows), ptr(part_w), stream_ptr()), "dmp_bwd_h1_w")
@@ -2078,6 +2115,24 @@ class _FusedDMPLayer(torch.autograd.Function):
         with deferred_reductions():
             # ---- edge side, down to the gathered node projections
             mfma, typed = mfma_ok(ix, H), typed_ok(ix, H)
+            l0_XX = None     # (XX, codes) once ``bwd_h1_w`` takes the last table's code weight gradient along
+
+            def l0_tables_full():
+                # every table has edge rows and node rows: every block of the code products is written
+                return all(r[1] > r[0] and n[1] > n[0] for _, r, n in ctx.l0_tables) and len(ctx.l0_tables) * ctx.l0.K == ctx.l0_W[0].size(0)
+
+            def l0_codes_buffer(H, device):
+                # [TK, 2H or 3H]: a table without edge rows leaves its block to the zeros
+                return (torch.empty if l0_tables_full() else torch.zeros)((ctx.l0_W[0].size(0), (3 if ctx.residual else 2) * H),
+                                                                            dtype=torch.float32, device=device)
+
+            def l0_codes_block(H, device, walked):
+                if not h1w_codes_ok(ctx.l0, ctx.l0_tables or (), walked):
+                    return None
+                t, rows, _ = ctx.l0_tables[-1]
+                XX, K0 = l0_codes_buffer(H, device), ctx.l0.K
+                return XX, dict(enc=ctx.l0.enc, K=K0, coef_e=ix.edge_select(coef)[2], rows=rows, residual=ctx.residual, out=XX[t * K0:(t + 1) * K0])
+
             if lazy is not None:
                 T, emap, ep = lazy
                 if H % 4 == 0 and H <= 256:
@@ -2106,8 +2161,10 @@ class _FusedDMPLayer(torch.autograd.Function):
                             and (ctx.l0 is None or getattr(ctx.l0, "enc_mask", None) is not None))
                     lt = live_tiles(ix, coef, ctx.e_gate) if skip else None
                     if lt is not None and h1w_ok(dzn, H1e, H):
-                        # both products of the second Linear's backward from ONE pass over dO and H1 (csrc/dmp_h1w.hip)
-                        dG, dbe, db2e, dW2e = bwd_h1_w(dzn, eW2, H1e, ascending_tiles(ctx.e_gate) or lt, slope)
+                        # both products of the second Linear's backward from ONE pass over dO and H1 (csrc/dmp_h1w.hip) -- and, in
+                        # the first layer, the target table's code weight gradient over the same kept rows (``l0_bwd_w``'s launch)
+                        l0_XX = l0_codes_block(H, dzn.device, "kept")
+                        dG, dbe, db2e, dW2e = bwd_h1_w(dzn, eW2, H1e, ascending_tiles(ctx.e_gate) or lt, slope, codes=l0_XX and l0_XX[1])[:4]
                     elif lt is not None:      # over the kept edges' tiles only
                         dG, dbe, db2e = bwd_h1_typed(dzn, eW2, H1e, ascending_tiles(ctx.e_gate) or lt, slope)
                         # dO^T H1 over the kept edges' tiles: the class-tile weight-gradient kernel's first half (its class-scaled
@@ -2122,7 +2179,8 @@ class _FusedDMPLayer(torch.autograd.Function):
                     if it is not None:
                         # no gate at all (a model without a filter net: the reference's one-label datasets): every row is live --
                         # both products of the second Linear's backward in one launch over the identity tile list
-                        dG, dbe, db2e, dW2e = bwd_h1_w(dzn, eW2, H1e, it, slope)
+                        l0_XX = l0_codes_block(H, dzn.device, "all")
+                        dG, dbe, db2e, dW2e = bwd_h1_w(dzn, eW2, H1e, it, slope, codes=l0_XX and l0_XX[1])[:4]
                     else:
                         dW2e, db2e = atb_rows(dzn, H1e, ctx.e_gate)
                         dG, dbe = bwd_h1_mfma(dzn, eW2, H1e, coef, ix, both_halves=False, gate=ctx.e_gate, slope=slope)  # dG is dPre
@@ -2155,9 +2213,10 @@ class _FusedDMPLayer(torch.autograd.Function):
             if l0 is not None:   # z = enc W0: one pass over dPre (and the residual gradient) on the K-column factor
                 W0, WV0 = ctx.l0_W
                 K0, TK = l0.K, W0.size(0)
-                full = all(r[1] > r[0] and n[1] > n[0] for _, r, n in tables) and len(tables) * K0 == TK   # every table has edge rows and node rows
-                XX = (torch.empty if full else torch.zeros)((TK, (3 if ctx.residual else 2) * H), dtype=torch.float32, device=dG.device)
-                for t, rows, _ in tables:
+                full = l0_tables_full()
+                # (the last table's block may be there already: ``bwd_h1_w(codes=...)`` above made it in its launch)
+                XX = l0_XX[0] if l0_XX is not None else l0_codes_buffer(H, dG.device)
+                for t, rows, _ in (tables[:-1] if l0_XX is not None else tables):
                     if rows[1] > rows[0]:
                         # (the rows to add: those with a non-zero code row -- or, where dPre's rows under a zero gate were not
                         # stored, the rows the gate keeps: the same list the forward walked; a kept row with a zero code adds zeros)

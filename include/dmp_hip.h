@@ -1227,6 +1227,22 @@ int64_t dmp_bwd_h1_w_blocks(int64_t tiles_bound);
 int dmp_bwd_h1_w(const float *dO, int64_t ldo, const float *W2, int64_t ldw, const float *H1, int64_t ldh,
                  const int32_t *slot_edge, const int32_t *num_tiles, int64_t tiles_bound, int64_t E, int H, float slope,
                  float *dG, int64_t ldg, float *partial, float *partial_rows, float *partial_w, void *stream);
+/*
+ * dmp_bwd_h1_w for the FIRST layer, whose input rows are z = enc W0 (label codes): the same launch also emits, per workgroup,
+ *     partial_x [dmp_bwd_h1_w_blocks(tiles_bound), K * (residual ? 3 : 2) * H]  =  [enc^T dG | (coef_e (.) enc)^T dG | enc^T dO]
+ * (row k: the 2 or 3 blocks of H side by side -- dmp_l0_bwd_w's layout, summed by dmp_reduce_partials) over the rows of the tile list
+ * whose edge id lies in [r0, r1), one embedding table's range: what dmp_l0_bwd_w_rows makes from a second read of dG and dO.
+ * enc [E, lde >= K] with 1 <= K <= dmp_bwd_h1_w_max_codes() code columns (any fp32 values), coef_e [E]; every other argument and
+ * result as dmp_bwd_h1_w (dG and the three other partials are bit-identical to that entry's).  The column waves keep two more
+ * 32 x 32 accumulators each ([enc | coef_e enc]^T times their 32 columns of dG / of dO, bf16x6); dG reaches them as a bf16-piece
+ * image behind a second workgroup barrier per tile.
+ */
+int dmp_bwd_h1_w_max_codes(void);
+int dmp_bwd_h1_w_codes(const float *dO, int64_t ldo, const float *W2, int64_t ldw, const float *H1, int64_t ldh,
+                       const int32_t *slot_edge, const int32_t *num_tiles, int64_t tiles_bound, int64_t E, int H, float slope,
+                       float *dG, int64_t ldg, float *partial, float *partial_rows, float *partial_w,
+                       const float *enc, int64_t lde, int K, const float *coef_e, int64_t r0, int64_t r1, int residual,
+                       float *partial_x, void *stream);
 
 /*
  * The node side of a layer over the kept nodes' tiles (dmp_kept_rows(tiles = 1)) as ONE launch per pass (csrc/dmp_nodechain.hip;
