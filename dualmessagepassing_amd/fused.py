@@ -30,7 +30,7 @@ import threading
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _abi, _lib, gatememo, ops
+from . import _abi, _lib, gatememo, ops, side
 from ._lib import check, ptr, stream_ptr
 
 
@@ -703,7 +703,7 @@ def l0_rows(l0, W0, z):
     """The first layer's edge rows ``z``: as given, or -- when ``dmpnn.joint_rep`` left them out (``l0.z_from_codes``) and the layer
     did not take the launch that forms them in registers -- made here: the pattern's embedded rows (``l0.z_head``) over the target's
     from their label codes."""
-    if l0 is None or not getattr(l0, "z_from_codes", False):
+    if l0 is None or not l0.z_from_codes:
         return z
     n, K, H = l0.z_head.size(0), l0.K, W0.size(1)
     out = torch.empty((l0.enc.size(0), H), dtype=torch.float32, device=l0.enc.device)
@@ -1517,11 +1517,15 @@ class Layer0Codes:
     ``enc`` [E, Kpad]: the packed gated label codes of the union's edge rows (``l0_pack``), ``K`` of them per row;
     ``W`` [K, H]: the embedding table (edge rows = ``enc W``), or [2K, H] = the pattern's table over the target's, the
     pattern's rows being the first ``esplit`` edges / ``nsplit`` nodes.  Optionally the same for the node rows:
-    ``venc`` [N, Kvpad], ``VK``, ``WV`` [VK or 2 VK, H]."""
+    ``venc`` [N, Kvpad], ``VK``, ``WV`` [VK or 2 VK, H].
+    What ``dmpnn.joint_rep`` may add: ``z_from_codes`` (the target's edge rows are not in memory: ``l0_z_from_codes``) with
+    ``z_head`` (the pattern's embedded edge rows), ``enc_mask`` / ``venc_mask`` (``code_row_mask`` of ``enc`` / ``venc``)."""
 
-    def __init__(self, enc, K, W, esplit=0, nsplit=0, venc=None, VK=0, WV=None):
+    def __init__(self, enc, K, W, esplit=0, nsplit=0, venc=None, VK=0, WV=None, z_from_codes=False, z_head=None, enc_mask=None,
+                 venc_mask=None):
         self.enc, self.K, self.W, self.esplit, self.nsplit = enc, K, W, esplit, nsplit
         self.venc, self.VK, self.WV = venc, VK, WV
+        self.z_from_codes, self.z_head, self.enc_mask, self.venc_mask = z_from_codes, z_head, enc_mask, venc_mask
 
     def vtables(self, N):
         """-> one ``(table, node rows)`` per table of the node rows' embedding."""
@@ -1801,8 +1805,714 @@ def small_gemm_jobs(jobs):
     check(lib.dmp_small_gemm_jobs(J, len(jobs), stream_ptr()), "dmp_small_gemm_jobs")
 
 
+# ----------------------------------------------------------------------------- the fused layer: one call's facts, then its stages
+class _LayerCall:
+    """The immutable facts of one call of the fused layer, built once in ``_FusedDMPLayer.forward`` and kept on ``ctx``: what the
+    stages of both passes read and none of them writes.  What a stage MAKES travels through its arguments and its return value."""
+    __slots__ = ("index", "coef", "residual", "H", "N", "slope", "inner", "v_gate", "e_gate", "Bn", "bn", "Wx", "Wes", "be",
+                 "nW2", "nb2", "eW2", "eb2", "WesT", "nW2t", "eW2t", "l0", "W0", "WV0", "nd", "vpool", "epool")
+
+    def __init__(self, **facts):
+        for name in self.__slots__:
+            setattr(self, name, facts[name])
+
+
+# ---- forward stages, in the order ``_FusedDMPLayer.forward`` runs them
+def _kept_nodes(index, H, v_gate, l0):
+    """Stage: the nodes a 0 / 1 node gate keeps (``node_rows``), or None.  A node under a zero of a gate whose maker wiped the input
+    rows is a zero row in every layer, so its aggregate, its projections, its update and all of its gradient rows are dead -- the
+    node side runs on the kept nodes' tiles, the edge kernels read a dead node's (unwritten) rows as zeros."""
+    side.wait("nodes")      # (index builds issued ahead on the side stream, dmpnn.prefetch_joint_indexes: wait for a stage at its first use)
+    return node_rows(index, v_gate, H) if kept_node_path(index, H, v_gate, l0) else None
+
+
+def _xn_buffer(c, device):
+    """The node rows a layer hands out under ``c.nd``.  An INNER layer's xn is read by the next layer of this rep-net only, under the
+    same gate: the dead rows stay unwritten; the last layer's rows go to the caller: zeros there."""
+    return dead_rows_buffer((c.N, c.H), device) if (c.inner & 1) else torch.zeros((c.N, c.H), dtype=torch.float32, device=device)
+
+
+def _l0_param_products(c, node_pass, device):
+    """The parameter-only products of a first layer on the label codes in ONE launch: W0 Bn_in, W0 Bn_out, W0 [A | B], WV0 Wx
+    -> ``(M0, WP, WB, MV)``: ``WP`` with the node pass, ``WB`` (and, with node codes, ``MV``) without."""
+    l0, W0, WV0, H, Bn, Wx = c.l0, c.W0, c.WV0, c.H, c.Bn, c.Wx
+    K0, TK = l0.K, W0.size(0)
+    M0 = torch.empty((TK, 2 * H), dtype=torch.float32, device=device)
+    jobs = [(M0, [(W0, False, c.Wes, False)], None)]
+    WP = WB = MV = None
+    if node_pass:
+        # ... written straight into the node pass's packed matrix, one per embedding table: rows 0 .. VK-1 = WV0 Wx (three
+        # column blocks), then K0 rows W0 Bn_in and K0 rows W0 Bn_out in the first block; zeros elsewhere
+        VK = l0.VK
+        WP = torch.zeros((TK // K0, L0_NODE_MAX_COLS, 3 * H), dtype=torch.float32, device=device)
+        for t in range(TK // K0):
+            WVt = WV0 if WV0.size(0) == VK else WV0[t * VK:(t + 1) * VK]
+            jobs += [(WP[t, :VK], [(WVt, False, Wx, False)], None),
+                     (WP[t, VK:VK + K0, :H], [(W0[t * K0:(t + 1) * K0], False, Bn[:H], False)], None),
+                     (WP[t, VK + K0:VK + 2 * K0, :H], [(W0[t * K0:(t + 1) * K0], False, Bn[H:], False)], None)]
+    else:
+        WB = torch.empty((2, TK, H), dtype=torch.float32, device=device)
+        jobs += [(WB[0], [(W0, False, Bn[:H], False)], None), (WB[1], [(W0, False, Bn[H:], False)], None)]
+        if l0.venc is not None:
+            MV = torch.empty((WV0.size(0), 3 * H), dtype=torch.float32, device=device)
+            jobs.append((MV, [(WV0, False, Wx, False)], None))
+    small_gemm_jobs(jobs)
+    return M0, WP, WB, MV
+
+
+def _node_first_codes(c, x, z):
+    """Stage, codes variant (dmpnn.py:113,121,125 + fn.sum + 129-136): the node side of a first layer on the label codes up to
+    ``H1n`` and the gathered projections -> ``(S0, M0, tables, H1n, P, ldp)``.  Sum of z over a node's edges = (sum of the label
+    codes) W0:  S = [S0_in W0 | S0_out W0] is never built,  S Bn = S0_in (W0 Bn_in) + S0_out (W0 Bn_out), two K-column products."""
+    l0, nd, H, N, W0 = c.l0, c.nd, c.H, c.N, c.W0
+    enc0, K0 = l0.enc, l0.K
+    tables = l0.tables(z.size(0), N)
+    if nd is not None and enc0.size(1) % 4 == 0:
+        # (the code sums of the kept nodes only: every reader -- the node pass over the kept list, the backward's masked
+        # K-column products -- leaves the dead nodes' rows out)
+        S0 = ops.seg_sum_raw(enc0, c.index.in_ptr, c.index.in_ent, N, None, True, -1.0, 1.0,
+                             out=dead_rows_buffer((N, 2 * enc0.size(1)), z.device), rows=nd.rows, tag="seg_sum2_codes")
+    else:
+        S0 = ops.seg_sum_raw(enc0, c.index.in_ptr, c.index.in_ent, N, None, True, -1.0, 1.0)    # [N, 2 Kpad] = [in | out]
+    Kp = enc0.size(1)
+    node_pass = (l0.venc is not None and H in MFMA_WIDTHS and l0.VK + 2 * K0 <= L0_NODE_MAX_COLS and W0.size(0) // K0 <= 2)
+    M0, WP, WB, MV = _l0_param_products(c, node_pass, z.device)
+    if node_pass:
+        # the whole node side before the second Linear in ONE pass over the codes: H1n and the two projection blocks
+        # (the kept nodes' H1n rows only; a dead node's projection rows are zeros)
+        H1n = dead_rows_buffer((N, H), z.device) if nd is not None else torch.empty((N, H), dtype=torch.float32, device=z.device)
+        PX = torch.empty((N, 2 * H), dtype=torch.float32, device=z.device)      # the gathered projections [P_dst | P_src]
+        for t, _, (n0, n1) in tables:
+            if n1 > n0 and (nd is None or n1 <= nd.prefix):      # (no gate, or the pattern's nodes -- all kept: every row)
+                l0_node_fwd(l0.venc, l0.VK, S0, K0, Kp, WP[t], c.bn, c.slope, None, n0, n1, H, H1n, PX)
+            elif n1 > n0:
+                l0_node_fwd(l0.venc, l0.VK, S0, K0, Kp, WP[t], c.bn, c.slope, nd.mask, n0, n1, H, H1n, PX, rows=nd.rows,
+                            q_begin=min(nd.prefix, n0))
+        return S0, M0, tables, H1n, PX, 2 * H
+    SB = torch.empty((N, H), dtype=torch.float32, device=z.device)
+    for t, _, (n0, n1) in tables:      # (N-row products: the small-product kernel is built for a few hundred rows)
+        if n1 > n0:
+            torch.mm(S0[n0:n1, :K0], WB[0, t * K0:(t + 1) * K0], out=SB[n0:n1])
+            SB[n0:n1].addmm_(S0[n0:n1, Kp:Kp + K0], WB[1, t * K0:(t + 1) * K0])
+    if l0.venc is not None:     # x Wx = venc (WV0 Wx): three column blocks of K-column products
+        VK = l0.VK
+        XP = torch.empty((N, 3 * H), dtype=torch.float32, device=z.device)
+        for t, (n0, n1) in l0.vtables(N):
+            smallk_embed(l0.venc[n0:n1, :VK], MV[t * VK:(t + 1) * VK], None, XP[n0:n1], H)
+    else:
+        XP = x @ c.Wx
+    return S0, M0, tables, add_bias_relu_(SB, XP[:, :H], c.bn, c.slope), XP[:, H:], 3 * H
+
+
+def _node_first_rows(c, x, z):
+    """Stage, rows variant (dmpnn.py:113,121,125 + fn.sum + 129-136): ``S`` over the (kept) CSR, then the node side up to ``H1n`` and
+    the gathered projections -> ``(S, H1n, P, ldp, xn, chain_panels)``; the last two only where the kept-node chain ran, which
+    makes ``xn`` in the same launch."""
+    nd, H, N, Bn, Wx, e_gate = c.nd, c.H, c.N, c.Bn, c.Wx, c.e_gate
+    # (input rows under a zero of a gate whose maker wiped them -- ``zero_rows_gate`` -- are zeros: not fetched)
+    side.wait("keepcsr")
+    kc = keep_in_csr(c.index, e_gate) if zero_rows_gate(e_gate) else None
+    if kc is not None and nd is not None:   # ... and over the kept NODES' rows only: the others' aggregates are dead
+        # (measured twice -- before and after the remap fix of finding (u): row pointers by list position,
+        # ``NodeRows.kept_incidence(in_only=True)``, one dependent load less per row group, leave the launch where it is)
+        S = ops.seg_sum_raw(z, kc[0], kc[1], N, None, True, -1.0, 1.0, out=dead_rows_buffer((N, 2 * H), z.device), rows=nd.rows)
+    elif kc is not None:      # the CSR over the kept edges: the plain kernel, no entries of skipped rows in its stream
+        S = ops.seg_sum_raw(z, kc[0], kc[1], N, None, True, -1.0, 1.0)
+    else:
+        S = ops.seg_sum_raw(z, c.index.in_ptr, c.index.in_ent, N, e_gate.reshape(-1) if zero_rows_gate(e_gate) else None, True, -1.0, 1.0)
+    if nd is None:
+        SB = S @ Bn
+        XP = x @ Wx
+        return S, add_bias_relu_(SB, XP[:, :H], c.bn, c.slope), XP[:, H:], 3 * H, None, None
+    # the node side on the kept nodes' tiles (the tile kernel with a plain panel, 128-wide block products; independent
+    # products share a launch): H1n = act(x Wx0 + S_in Bn_in + S_out Bn_out + bn) as two partial products + a third
+    # that adds them up, the two gathered projection blocks, xn = x + (H1n W2^T + b2) -- nothing is read or written
+    # for the other nodes
+    T = nd.tiles
+    H1n = dead_rows_buffer((N, H), z.device)
+    if node_chain_ok(H, x, S, Bn, Wx, c.nW2):
+        # ... as ONE launch: the rows stay in the workgroup, the six panels stream through LDS (csrc/dmp_nodechain.hip) --
+        # the partial products x Wx0 + bn and S_in Bn_in never go through memory
+        PX = dead_rows_buffer((N, 2 * H), z.device)      # [P_dst | P_src]
+        xn = _xn_buffer(c, z.device)
+        chain_panels = node_chain_panels(Bn, Wx, c.nW2)    # (both passes' panels: one launch per layer and step)
+        node_chain_fwd(x, S, chain_panels[0], c.bn, c.nb2, c.residual, c.slope, T, H1n, PX, xn)
+        return S, H1n, PX, 2 * H, xn, chain_panels
+    XP = dead_rows_buffer((N, 3 * H), z.device)          # [x Wx0 + bn (a partial) | P_dst | P_src]
+    T1 = dead_rows_buffer((N, H), z.device)
+    typed_jobs([dict(a=x, W=Wx[:, :H], bias=c.bn, out=XP[:, :H]), dict(a=S[:, :H], W=Bn[:H], out=T1),
+                dict(a=x, W=Wx[:, H:2 * H], out=XP[:, H:2 * H]), dict(a=x, W=Wx[:, 2 * H:], out=XP[:, 2 * H:])], T)
+    out_fwd_typed(S[:, H:], Bn[H:], None, XP[:, :H], T, out=H1n, slope=c.slope, prev2=T1)
+    return S, H1n, XP[:, H:], 3 * H, None, None
+
+
+def _node_out(c, x, H1n):
+    """Stage (dmpnn.py:137-140): the node side's second Linear + gate + residual -> ``xn`` (where the chain did not make it)."""
+    prev = x if c.residual else None
+    if c.nd is not None:
+        xn = _xn_buffer(c, x.device)
+        if c.nW2t is not None:
+            return out_fwd_typed(H1n, c.nW2t, c.nb2, prev, c.nd.tiles, out=xn)
+        return out_fwd_typed(H1n, c.nW2, c.nb2, prev, c.nd.tiles, out=xn, w_in_out=False)
+    if onepanel_ok(c.H):   # Linear + gate + residual in one fused MFMA kernel, as on the edge side
+        return out_fwd_mfma(H1n, c.nW2, c.nb2, c.v_gate, prev, c.nW2t)
+    return gate_residual(prev, torch.addmm(c.nb2, H1n, c.nW2.t()), c.v_gate)
+
+
+def _dead_edge_rows_of(c):
+    """``(dead_gate, dead)`` of the edge side's forward: the gate whose zeros mark dead rows of H1e (the two producers of H1e leave
+    them out), or None; and what is dead beside them -- 0: nothing, 1: z's rows under the gate's zeros (a gate whose maker wiped the
+    rep-net's input rows, ``zero_rows_gate``: zeros, not fetched), 3: as an INNER layer of a rep-net (the next layer of the same
+    rep-net, under the same gate, is the only reader of zn) the output's zero rows as well: not stored either."""
+    dead_gate = c.e_gate if dead_h1_rows(c.index, c.H, c.e_gate) else None
+    dead_in = dead_gate is not None and dead_edge_rows(c.index, c.H, c.e_gate)
+    return dead_gate, (3 if (c.inner & 1) else 1) if dead_in else 0
+
+
+def _residual_from_codes(c, H1e):
+    """The target's residual rows z = enc W0 are not in memory at all (``dmpnn.joint_rep`` did not make them): the second Linear adds
+    them as one more k-group over their codes (``out_fwd_typed_codes``); the pattern's few rows (their own table) come in as the
+    residual operand."""
+    l0 = c.l0
+    return bool(l0 is not None and c.residual and l0.z_from_codes and out_codes_ok(H1e, l0.enc, l0.K, c.W0[-l0.K:]))
+
+
+def _edge_out_tiles(c, like, dead, codes):
+    """The launch of the edge side's second Linear, decided ONCE (by whichever stage issues it): the tile list it walks, or None --
+    ``out_fwd_mfma`` over all rows.  With ``dead == 3`` nothing is written for the rows under a zero gate: the kept edges' class
+    tiles (``live_tiles``: the first Linear, where it rides in the launch, needs the class scale per tile; a launch with a plain
+    panel needs no class and walks ``ascending_tiles(c.e_gate) or`` these).  Without any gate (the all-rows step) a first layer whose
+    residual comes from the ``codes``: the same launch over the identity tile list.  ``like``: any tensor of the edge rows."""
+    if dead == 3 and c.eW2t is not None:
+        lt = live_tiles(c.index, c.coef, c.e_gate)
+        if lt is not None:
+            return lt
+    if codes and c.e_gate is None and c.eW2t is not None:
+        return identity_tiles(like.size(0), like.device)
+    return None
+
+
+def _edge_first_codes(c, z, M0, tables, P, ldp, sums_only):
+    """Stage, codes variant (dmpnn.py:112,120,124 + 142-152): the edge side's first Linear from the label codes -> ``(H1e, zn)``;
+    ``zn`` is None unless the second Linear's launch took the first along."""
+    l0, H, W0 = c.l0, c.H, c.W0
+    enc0, K0 = l0.enc, l0.K
+    side.wait("erows")      # (a layer on the label codes needs the tiles only for its second Linear)
+    dead_gate, dead = _dead_edge_rows_of(c)
+    H1e = dead_rows_buffer((z.size(0), H), z.device) if dead_gate is not None else torch.empty((z.size(0), H), dtype=torch.float32, device=z.device)
+    # the one-launch edge MLP stands exactly where the route is l0_edge_fwd per table + out_fwd_typed_codes (``_edge_out``): over the
+    # kept edges' tiles under the gates (whose zero rows are dead rows of H1e: the per-table launches leave them out as well,
+    # where their mask starts at a whole word), over the identity tiles without a gate
+    # (212 against 275 us for the launches of their own; the first build was time-neutral here: docs/HISTORY.md (oo))
+    codes = _residual_from_codes(c, H1e)
+    if (codes and not sums_only and c.eW2t is not None
+            and l0_edge_mlp_ok(H, K0, W0.size(0) // K0, enc0, P, c.eW2t, l0.z_head)):
+        if dead == 3:
+            side.wait("tiles")
+        tiles = _edge_out_tiles(c, H1e, dead, codes)
+        if tiles is not None:
+            # both Linears as ONE launch: H1e goes from the first to the second on the chip, the code rows are fetched once
+            # (through the second Linear's wrapper, as every E-row Linear + residual launch goes: it fills H1e on the way)
+            zn = out_fwd_typed_codes(H1e, c.eW2t, c.eb2, enc0, K0, W0[-K0:], ascending_tiles(c.e_gate) or tiles, prev=l0.z_head,
+                                     row0=l0.z_head.size(0),
+                                     first=dict(M=M0, tables=W0.size(0) // K0, split=l0.esplit, P=P, ldp=ldp, bias=c.be, coef=c.coef,
+                                                index=c.index, slope=c.slope))
+            return H1e, zn
+    for t, rows, _ in tables:
+        if rows[1] > rows[0]:
+            l0_edge_fwd(enc0, K0, M0[t * K0:(t + 1) * K0], P, ldp, c.be, c.coef, c.index, c.slope, rows, H1e,
+                        mask=gate_row_mask(dead_gate) if dead_gate is not None else None)
+    return H1e, None
+
+
+def _edge_first_rows(c, z, P, ldp, sums_only):
+    """Stage, rows variant (dmpnn.py:112,120,124 + 142-152): the edge side's first Linear on the edge rows -> ``(H1e, zn)``; ``zn``
+    is None unless the second Linear's launch took the first along -- or the un-typed route made it with the library."""
+    H, nd = c.H, c.nd
+    side.wait("tiles")
+    dead_gate, dead = _dead_edge_rows_of(c)
+    sel = None if nd is None else nd.sel
+    # the one-launch edge MLP stands exactly where the route is edge_fwd_typed + out_fwd_typed over the kept edges' tiles
+    # (``_edge_out`` with dead == 3, live_tiles and the folded W2^T): a gated INNER layer whose edge rows are wanted, with its residual
+    if not sums_only and c.residual and edge_mlp_fwd_ok(H, z, P, c.eW2t):
+        tiles = _edge_out_tiles(c, z, dead, False)
+        if tiles is not None:
+            # both Linears over the kept edges' class tiles as ONE launch: H1e goes from the first to the second on the chip
+            # (through the second Linear's wrapper, as every E-row Linear + residual launch goes: it fills H1e on the way)
+            H1e = dead_rows_buffer((z.size(0), H), z.device)
+            zn = out_fwd_typed(H1e, c.eW2t, c.eb2, z, tiles,
+                               first=dict(z=z, Wes=c.Wes, P=P, ldp=ldp, bias=c.be, coef=c.coef, index=c.index, slope=c.slope, sel=sel))
+            return H1e, zn
+    if typed_ok(c.index, H):
+        # (under ``nd`` the projection rows of the dead nodes were never written: their selectors read as zeros)
+        return edge_fwd_typed(z, c.Wes, P, ldp, c.be, c.coef, c.index, c.slope, dead_gate=dead_gate, sel=sel), None
+    G = z @ c.Wes
+    H1e = edge_combine_raw(G, 2 * H, P, ldp, c.be, c.coef, c.index, H, relu=True, slope=c.slope)
+    del G
+    if sums_only:
+        return H1e, None
+    Oe = torch.addmm(c.eb2, H1e, c.eW2.t())
+    return H1e, gate_residual(z if c.residual else None, Oe, c.e_gate)
+
+
+def _edge_out(c, z, H1e):
+    """Stage (dmpnn.py:153-156): the edge side's second Linear + gate + residual -> ``zn``, where no launch has made it yet."""
+    l0 = c.l0
+    _, dead = _dead_edge_rows_of(c)
+    side.wait("tiles")
+    codes = _residual_from_codes(c, H1e)
+    tiles = _edge_out_tiles(c, H1e, dead, codes)
+    if tiles is None:
+        return out_fwd_mfma(H1e, c.eW2, c.eb2, c.e_gate, l0_rows(l0, c.W0, z) if c.residual else None, c.eW2t, dead_rows=dead)
+    # (a plain panel needs no class: the kept edges' tiles in ascending row order -- ``ascending_tiles``)
+    walk = ascending_tiles(c.e_gate) or tiles
+    if codes:
+        return out_fwd_typed_codes(H1e, c.eW2t, c.eb2, l0.enc, l0.K, c.W0[-l0.K:], walk, prev=l0.z_head, row0=l0.z_head.size(0))
+    return out_fwd_typed(H1e, c.eW2t, c.eb2, l0_rows(l0, c.W0, z) if c.residual else None, walk)
+
+
+def _pooled_outputs(c, z, xn, zn, H1e, sums_only):
+    """Stage (the LAST layer under pooling heads): the per-graph sums of both outputs -> ``(vs, es, gcnt)``; ``gcnt``: the gated
+    row counts per graph of the row-less form (``sums_only``: no ``zn``), which the backward's db2 needs again."""
+    H, epool, e_gate, eW2, eb2 = c.H, c.epool, c.e_gate, c.eW2, c.eb2
+    vs = pool_rows(xn, c.vpool) if c.vpool is not None else None
+    if not sums_only:
+        return vs, (pool_rows(zn, epool) if epool is not None else None), None
+    halves = 2 if epool.flag8 is not None else 1
+    G_ = epool.num_graphs
+    Q = pool_rows(H1e, epool, e_gate).view(G_ * halves, H)                      # sum of g H1 per graph (and flag)
+    gcnt = pool_weight_sums(epool, e_gate)                                       # sum of g per graph (and flag)
+    cnt = gcnt.view(G_ * halves, 1)
+    # (z's rows under a zero of a gate whose maker wiped the input are zeros, and as an inner layer's output not even
+    # written: weight 0, not fetched)
+    zs = pool_rows(z, epool, e_gate if zero_rows_gate(e_gate) else None).view(G_ * halves, H) if c.residual else None
+    if Q.is_contiguous() and eW2.is_contiguous() and Q.size(0) <= SMALL_GEMM_MAX_ROWS:
+        es = torch.empty((G_ * halves, H), dtype=torch.float32, device=Q.device)  # Q W2^T + cnt b2 (+ sum of z): one launch
+        small_gemm_jobs([(es, [(Q, False, eW2, True), (cnt, False, eb2.view(1, H), False)], zs)])
+    else:
+        # (thousands of graphs: the small-product kernel is built for a few hundred rows -- 43 us at 4096 rows against
+        # 13 for a library product + one row pass)
+        es = torch.addmm(zs, Q, eW2.t()) if c.residual else Q @ eW2.t()
+        es.addcmul_(cnt, eb2.view(1, H))
+    # ... of which only the NON-FLAGGED half is returned ([G, H]): without the rows the backward propagates a gradient
+    # through that half only (the row map is -1 for flagged rows), so the flagged sums are not handed out as if they
+    # were differentiable (the heads mask reversed edges out and read [:, :H] anyway, basemodel.py:1545-1631)
+    return vs, es.view(G_, halves * H)[:, :H], gcnt
+
+
+# ---- backward stages, in the order ``_FusedDMPLayer.backward`` runs them
+def _grad_seeds(c, x, z, H1e, dxn, dzn, dvs, des, typed):
+    """Stage: the gradients through the pooled sums (last layer) -> ``(dxn, dzn, lazy)``.  Node side: expanded (N rows are cheap).
+    Edge side: if the sums are the ONLY consumer of zn, dzn[e] = T[graph of e] (zero for reversed edges) with T = des[:, :H] and
+      dH1 = (g (.) dzn) W2 = g[e] (T W2)[graph of e]             -> no E-row product, no [E, H] gradient tensor
+      dW2 = (g (.) dzn)^T H1 = T^T Q,  Q[b] = sum_{e in b} g[e] H1[e]   -> one pooled pass over H1
+      db2 = T^T (sum_{e in b} g[e])
+    and the residual term of dz reads T through the row map: ``lazy = (T, row map, pool index)``, ``dzn`` stays None."""
+    H = c.H
+    lazy = None
+    if dvs is not None:
+        exp = ops.gather_rows_raw(dvs.contiguous(), c.vpool.seg32)
+        dxn = exp if dxn is None else dxn + exp
+    if des is not None:
+        ep = c.epool
+        if dzn is None and typed and H1e.size(0) > 0 and des.size(1) == H:
+            # des is [G, H]: the row-less forward hands out the non-flagged sums only, or no flag splits the sums.  A
+            # [G, 2H] gradient (forward with rows, flag-split sums) may carry a flagged half: the expanded path below
+            lazy = (des.contiguous(), pool_rowmap(ep), ep)
+        else:
+            if ep.flag8 is not None and des.size(1) == H:     # the row-less forward's [G, H]: nothing flows to the flagged rows
+                des = torch.cat([des, torch.zeros_like(des)], dim=1)
+            exp = (ops.gather_select_raw(des.contiguous(), ep.seg32, ep.flag8, H, None, 1.0, 1.0) if ep.flag8 is not None
+                   else ops.gather_rows_raw(des.contiguous(), ep.seg32))
+            dzn = exp if dzn is None else dzn + exp
+    if dxn is None:
+        dxn = torch.zeros_like(x)
+    if dzn is None and lazy is None:
+        dzn = torch.zeros_like(z)
+    return dxn.contiguous(), (dzn.contiguous() if dzn is not None else None), lazy
+
+
+def l0_tables_full(l0, tables, W0):
+    """Every table has edge rows and node rows: every block of the first layer's code products is written."""
+    return all(r[1] > r[0] and n[1] > n[0] for _, r, n in tables) and len(tables) * l0.K == W0.size(0)
+
+
+def l0_codes_buffer(l0, tables, W0, residual, H, device):
+    """[TK, 2H or 3H] for ``enc^T [dPre | c dPre (| dzn)]``: a table without edge rows leaves its block to the zeros."""
+    return (torch.empty if l0_tables_full(l0, tables, W0) else torch.zeros)((W0.size(0), (3 if residual else 2) * H),
+                                                                           dtype=torch.float32, device=device)
+
+
+def l0_codes_block(c, tables, device, walked):
+    """``(XX, codes)`` where ``bwd_h1_w`` takes the last table's code weight gradient along (``h1w_codes_ok``), else None: the
+    buffer of ``l0_codes_buffer`` and the ``codes=`` argument that writes the table's block of it."""
+    if not h1w_codes_ok(c.l0, tables or (), walked):
+        return None
+    t, rows, _ = tables[-1]
+    XX, K0 = l0_codes_buffer(c.l0, tables, c.W0, c.residual, c.H, device), c.l0.K
+    return XX, dict(enc=c.l0.enc, K=K0, coef_e=c.index.edge_select(c.coef)[2], rows=rows, residual=c.residual, out=XX[t * K0:(t + 1) * K0])
+
+
+def _edge_out_bwd_lazy(c, H1e, lazy, gcnt):
+    """The edge side's second Linear backward from the per-graph table alone (``_grad_seeds``) -> ``(dG, dbe, dW2e, db2e)``."""
+    H, e_gate = c.H, c.e_gate
+    T, emap, ep = lazy
+    if H % 4 == 0 and H <= 256:
+        # (dPre's rows under a zero of a 0 / 1 gate: every reader below leaves them out -- the kept incidence sums,
+        # the class-tile kernels over the kept edges' tiles)
+        skip = c.l0 is None and c.nd is not None and USE_PLAIN_ATB and dead_edge_rows(c.index, H, e_gate, c.coef)
+        dG, dbe, Q = pool_relu_bwd(T @ c.eW2, emap, e_gate, H1e, ep, c.slope, skip_dead=skip)       # dG is dPre; one pass over H1e
+        Q = Q[:, :H]
+    else:
+        dG, dbe = relu_bwd_gathered_colsum(T @ c.eW2, emap, e_gate, H1e, c.slope)
+        Q = pool_rows(H1e, ep, e_gate)[:, :H]
+    dW2e = T.t() @ Q
+    if gcnt is None:        # gated row counts per graph
+        gcnt = pool_weight_sums(ep, e_gate)
+    return dG, dbe, dW2e, gcnt[:, 0] @ T
+
+
+def _edge_out_bwd_typed(c, tables, H1e, dzn):
+    """The edge side's second Linear backward on the tile / one-panel kernels -> ``(dG, dbe, dW2e, db2e, l0_XX)``.  The gate is
+    applied inside the two consumers of dO = gate * dzn (no [E,H] pass of its own).  ``l0_XX``: ``l0_codes_block`` once
+    ``bwd_h1_w`` took the last table's code weight gradient along, else None."""
+    ix, coef, H, slope, e_gate, eW2 = c.index, c.coef, c.H, c.slope, c.e_gate, c.eW2
+    l0_XX = None
+    if binary_gate_mask(e_gate) is not None:
+        # a 0 / 1 gate: bwd_h1 hands out sum_e g_e dzn[e] (db2) from the rows it fetches anyway, and the weight
+        # gradient runs ungated over the masked-in rows on the bf16 pipe
+        # (dPre's zero rows are not stored: the class-tile kernels, the scatter-add and the layer-0 products below
+        # leave them out)
+        skip = USE_MASKED_SUMS and dead_h1_rows(ix, H, e_gate) and (c.l0 is None or c.l0.enc_mask is not None)
+        lt = live_tiles(ix, coef, e_gate) if skip else None
+        if lt is not None and h1w_ok(dzn, H1e, H):
+            # both products of the second Linear's backward from ONE pass over dO and H1 (csrc/dmp_h1w.hip) -- and, in
+            # the first layer, the target table's code weight gradient over the same kept rows (``l0_bwd_w``'s launch)
+            l0_XX = l0_codes_block(c, tables, dzn.device, "kept")
+            dG, dbe, db2e, dW2e = bwd_h1_w(dzn, eW2, H1e, ascending_tiles(e_gate) or lt, slope, codes=l0_XX and l0_XX[1])[:4]
+        elif lt is not None:      # over the kept edges' tiles only
+            dG, dbe, db2e = bwd_h1_typed(dzn, eW2, H1e, ascending_tiles(e_gate) or lt, slope)
+            # dO^T H1 over the kept edges' tiles: the class-tile weight-gradient kernel's first half (its class-scaled
+            # second half costs no further products) -- no tiles' worth of zero rows in between
+            dW2e = atb_typed(dzn, H1e, coef, ix, gate=e_gate, plain=True)
+        else:
+            dG, dbe, db2e = bwd_h1_mfma(dzn, eW2, H1e, coef, ix, both_halves=False, gate=e_gate, slope=slope, rows_colsum=True,
+                                        skip_dead_stores=skip)
+            dW2e = atb_rows(dzn, H1e, e_gate, colsum=False)[0]
+        return dG, dbe, dW2e, db2e, l0_XX
+    it = identity_tiles(dzn.size(0), dzn.device) if (e_gate is None and h1w_ok(dzn, H1e, H)) else None
+    if it is not None:
+        # no gate at all (a model without a filter net: the reference's one-label datasets): every row is live --
+        # both products of the second Linear's backward in one launch over the identity tile list
+        l0_XX = l0_codes_block(c, tables, dzn.device, "all")
+        dG, dbe, db2e, dW2e = bwd_h1_w(dzn, eW2, H1e, it, slope, codes=l0_XX and l0_XX[1])[:4]
+    else:
+        dW2e, db2e = atb_rows(dzn, H1e, e_gate)
+        dG, dbe = bwd_h1_mfma(dzn, eW2, H1e, coef, ix, both_halves=False, gate=e_gate, slope=slope)  # dG is dPre
+    return dG, dbe, dW2e, db2e, l0_XX
+
+
+def _edge_out_bwd(c, tables, H1e, dzn, lazy, gcnt, typed):
+    """Stage: the edge side, down to the gathered node projections -- the second Linear's backward and the activation's
+    -> ``(dG, dbe, dW2e, db2e, l0_XX)``; ``dG[:, :H]`` is dPre."""
+    if lazy is not None:
+        return _edge_out_bwd_lazy(c, H1e, lazy, gcnt) + (None,)
+    if typed:
+        return _edge_out_bwd_typed(c, tables, H1e, dzn)
+    dOe, db2e = scale_rows_colsum(dzn, c.e_gate)
+    dW2e = atb(dOe, H1e)
+    dH1e = dOe @ c.eW2
+    dG, dbe = relu_bwd_g_colsum(dH1e, H1e, c.coef, c.index.dst32, c.slope)
+    return dG, dbe, dW2e, db2e, None
+
+
+def _endpoint_sums(c, dG, typed, device):
+    """Stage: dPre into both endpoints' rows, the backward scatter-add (dPre's rows under a zero edge gate are zeros: not fetched)
+    -> ``dXP`` = [dPn | dP] with its last two column blocks written: the node side writes dPn in place, no concatenation (under
+    ``c.nd``: the kept nodes' rows only)."""
+    ix, H, N, nd, e_gate = c.index, c.H, c.N, c.nd, c.e_gate
+    dXP = dead_rows_buffer((N, 3 * H), device) if nd is not None else torch.empty((N, 3 * H), dtype=torch.float32, device=device)
+    sums_masked = typed and USE_MASKED_SUMS and has_row_mask(e_gate)
+    # (... and the rows of the dead nodes are neither summed nor stored)
+    if kept_incidence_sums(ix, H, e_gate, nd is not None):
+        # every kept node's two sums over its KEPT edges (the incidence CSR over the kept edges, a row per kept node):
+        # the plain segment-sum kernel, ascending edge id -- an edge row without a kept endpoint is never fetched
+        kp, ke = nd.kept_incidence(ix, e_gate)
+        ops.seg_sum_raw(dG[:, :H], kp, ke, N, None, True, 1.0, -1.0, out=dXP[:, H:], rows=nd.rows, ptr_by_pos=True, tag="seg_sum2_kept_inc",
+                        incidence=True)
+    else:
+        nodes = (nd.mask, nd.sel[:2]) if (nd is not None and sums_masked and ops.graph_seg_ok(ix, dG[:, :H], H, dXP[:, H:])) else None
+        ops.endpoint_sums(dG[:, :H], ix, out=dXP[:, H:], mask=gate_row_mask(e_gate) if sums_masked else None,
+                          gate=e_gate if sums_masked else None, nodes=nodes)
+    return dXP
+
+
+def _l0_edge_code_products(c, tables, dG, dzn, l0_XX):
+    """Stage, codes variant: z = enc W0 -- one pass over dPre (and the residual gradient) on the K-column factor -> ``XX`` =
+    enc^T [dPre | c dPre (| dzn)] per table.  (The last table's block may be there already: ``bwd_h1_w(codes=...)`` made it in its
+    launch, ``l0_XX``.)"""
+    l0, e_gate, K0 = c.l0, c.e_gate, c.l0.K
+    XX = l0_XX[0] if l0_XX is not None else l0_codes_buffer(l0, tables, c.W0, c.residual, c.H, dG.device)
+    for t, rows, _ in (tables[:-1] if l0_XX is not None else tables):
+        if rows[1] > rows[0]:
+            # (the rows to add: those with a non-zero code row -- or, where dPre's rows under a zero gate were not
+            # stored, the rows the gate keeps: the same list the forward walked; a kept row with a zero code adds zeros)
+            l0_bwd_w(l0.enc, K0, c.index.edge_select(c.coef)[2], dG, dzn if c.residual else None, rows, XX[t * K0:(t + 1) * K0],
+                     mask=(gate_row_mask(e_gate) if (l0.enc_mask is not None and binary_gate_mask(e_gate) is not None)
+                           else l0.enc_mask))
+    return XX
+
+
+def _edge_first_wgrad(c, z, dG, typed, want_dz):
+    """Stage, rows variant: the first Linear's weight gradient [H,2H] = [dA_e | dB_e] -- or None: with the input gradient still to
+    come (``_edge_input_grad``, over the same tile list) both products of dPre run in ONE launch there, ``bwd_z_w``: decided here,
+    made there.  (dG = dPre has zero rows under a zero edge gate, whichever kernel made it: the typed kernels skip those edges.)"""
+    ix, H, e_gate = c.index, c.H, c.e_gate
+    if typed and want_dz and H == 128 and (e_gate is None or dead_edge_rows(ix, H, e_gate, c.coef)):
+        return None
+    return atb_typed(z, dG, c.coef, ix, gate=e_gate) if typed else atb(z, dG)
+
+
+def _wgrad(a, b, kernel):
+    """A node-side weight gradient a^T b of its own: the MFMA kernel (``kernel``: ``atb_ok`` of the widest product) or library GEMMs."""
+    return atb_rows(a, b, colsum=False)[0] if kernel else atb(a, b)
+
+
+def _node_one_launch(c, x, S, H1n, dxn, dXP):
+    """The node side's weight gradients share one launch (``_node_wgrads``); the kept-node path has no other form."""
+    one_launch = onepanel_ok(c.H) and atb_ok(dxn, H1n) and atb_ok(x, dXP) and (S is None or atb_ok(S, dXP))
+    if c.nd is not None and not (one_launch and binary_gate_mask(c.v_gate) is not None):
+        raise _lib.DmpError("fused layer backward: the kept-node path needs the masked weight-gradient launch")
+    return one_launch
+
+
+def _node_out_bwd(c, dxn, H1n, dXP, own_dW2n, kernel):
+    """The node side's second Linear backward and the activation's -> ``(dPn, dbn, db2n, dW2n)``: ``dPn`` is written into
+    ``dXP[:, :H]``; ``dW2n`` only with ``own_dW2n`` (else it comes out of ``_node_wgrads``, with ``db2n`` where that is None here)."""
+    nd, H, slope, v_gate, nW2 = c.nd, c.H, c.slope, c.v_gate, c.nW2
+    dW2n = db2n = None
+    if nd is not None:
+        # dPn = act'(H1n) (.) (dxn W2) on the kept nodes' tiles; db2n = the column sums of the dxn rows it fetches
+        dPn, dbn, db2n = bwd_h1_typed(dxn, nW2, H1n, nd.tiles, slope, out=dXP[:, :H])
+        if own_dW2n:
+            dW2n = atb_rows(dxn, H1n, v_gate, colsum=False)[0]
+    elif onepanel_ok(H) and atb_ok(dxn, H1n):
+        # as on the edge side: the node gate lives inside the two consumers of dO = v_gate * dxn
+        if binary_gate_mask(v_gate) is not None:
+            # a 0 / 1 node gate: db2n from the rows bwd_h1 fetches, the weight gradient(s) ungated over the masked-in rows
+            dPn, dbn, db2n = bwd_h1_mfma(dxn, nW2, H1n, both_halves=False, gate=v_gate, out=dXP[:, :H], slope=slope,
+                                         rows_colsum=True)
+            if own_dW2n:
+                dW2n = atb_rows(dxn, H1n, v_gate, colsum=False)[0]
+        else:
+            if own_dW2n:
+                dW2n, db2n = atb_rows(dxn, H1n, v_gate)
+            dPn, dbn = bwd_h1_mfma(dxn, nW2, H1n, both_halves=False, gate=v_gate, out=dXP[:, :H], slope=slope)
+    else:
+        dOn, db2n = scale_rows_colsum(dxn, v_gate)
+        dW2n = _wgrad(dOn, H1n, kernel)
+        dH1n = dOn @ nW2
+        dPn, dbn = relu_bwd_colsum_(dH1n, H1n, out=dXP[:, :H], slope=slope)
+    return dPn, dbn, db2n, dW2n
+
+
+def _node_wgrads(c, products):
+    """The node side's weight gradients ``a^T b`` of ``products`` = [(dxn, H1n), (S, dPn) unless on the codes, (x, dXP)] (1 + 2 + 3
+    output blocks) in ONE launch -> ``(the gradients, db2n or None)``.  (dPn = act'(H1n) ((v_gate dxn) W2): zero rows under a zero
+    node gate -- all products but the last skip them.)"""
+    nd, v_gate = c.nd, c.v_gate
+    last = products[-1] + (None, False)
+    if nd is not None:
+        # the products over the kept nodes' tiles (rows gathered by slot): 41 % of the row tiles at bench.py's labels, and
+        # nothing of a dead node's (unwritten) rows is touched
+        res = atb_rows_multi([(a, b, None, False) for a, b in products], tiles=nd.tiles)
+        return [r[0] for r in res], None
+    vm = binary_gate_mask(v_gate)
+    if vm is not None:    # (db2n came from bwd_h1; no job carries a gate: the launch runs on the bf16 pipe)
+        res = atb_rows_multi([(a, b, None, False, vm) for a, b in products[:-1]] + [last])
+        return [r[0] for r in res], None
+    vm = gate_row_mask(v_gate)
+    res = atb_rows_multi([products[0] + (v_gate, True, vm)] + [(a, b, None, False, vm) for a, b in products[1:-1]] + [last])
+    return [r[0] for r in res], res[0][1]
+
+
+def _dx_buffer(c, device):
+    """The node input gradient under ``c.nd``.  A dead node's row is multiplied by the gate's zero further down: left unwritten where
+    the layer before is the only reader (``inner`` bit 1), zeros for whoever made the first layer's rows."""
+    return dead_rows_buffer((c.N, c.H), device) if (c.inner & 2) else torch.zeros((c.N, c.H), dtype=torch.float32, device=device)
+
+
+def _node_dS(c, dPn, dXP, dxn, want_dx):
+    """Rows variant: dS = dPn Bn^T -> ``(dS, dxU)``; ``dxU``: under ``c.nd`` with ``want_dx``, two of the three partial products of
+    dx = dxn + dXP Wx^T, made in the same launch (``_node_dx`` adds the third), else None."""
+    nd, H, N, Bn, Wx = c.nd, c.H, c.N, c.Bn, c.Wx
+    if nd is None:
+        return dPn @ Bn.t(), None
+    # dS = dPn Bn^T on the kept nodes' tiles; the edge kernel reads a dead node's rows as zeros
+    dS, dxU = dead_rows_buffer((N, 2 * H), dXP.device), None
+    jobs = [dict(a=dPn, W=Bn[:H], w_in_out=False, out=dS[:, :H]), dict(a=dPn, W=Bn[H:], w_in_out=False, out=dS[:, H:])]
+    if want_dx:    # ... and in the same launch two of the three partial products of dx = dxn + dXP Wx^T
+        dxU = dead_rows_buffer((N, 2 * H), dXP.device)
+        jobs += [dict(a=dXP[:, :H], W=Wx[:, :H], w_in_out=False, prev=dxn if c.residual else None, out=dxU[:, :H]),
+                 dict(a=dXP[:, H:2 * H], W=Wx[:, H:2 * H], w_in_out=False, out=dxU[:, H:])]
+    typed_jobs(jobs, nd.tiles)
+    return dS, dxU
+
+
+def _node_dx(c, dxn, dXP, dxU):
+    """dx = dxn + dXP Wx^T.  Under ``c.nd`` on the kept nodes' tiles: the third 128-deep block of the contraction + the two partial
+    products made beside dS (``dxU``) -- or, for a first layer on the label codes of its edge rows only (no dS launch to share:
+    ``dxU`` None), block after block."""
+    nd, H, Wx = c.nd, c.H, c.Wx
+    if nd is None:
+        return torch.addmm(dxn, dXP, Wx.t()) if c.residual else dXP @ Wx.t()
+    dx = _dx_buffer(c, dXP.device)
+    if dxU is not None:
+        return out_fwd_typed(dXP[:, 2 * H:], Wx[:, 2 * H:], None, dxU[:, :H], nd.tiles, out=dx, w_in_out=False, prev2=dxU[:, H:])
+    for b3 in range(3):
+        out_fwd_typed(dXP[:, b3 * H:(b3 + 1) * H], Wx[:, b3 * H:(b3 + 1) * H], None,
+                      (dxn if c.residual else None) if b3 == 0 else dx, nd.tiles, out=dx, w_in_out=False)
+    return dx
+
+
+def _node_bwd_rows(c, chain_panels, x, S, H1n, dxn, dXP, want_dx):
+    """Stage, rows variant: the node side backward -> ``(dBn, dbn, dWx, dW2n, db2n, dS, dx)``: dPn with the bias gradients, dS,
+    the weight gradients, dx -- the kept-node chain makes all but the weight gradients in its one launch."""
+    nd, H = c.nd, c.H
+    one_launch, kernel = _node_one_launch(c, x, S, H1n, dxn, dXP), atb_ok(x, dXP)
+    chained = nd is not None and chain_panels is not None and node_chain_ok(H, dxn, H1n, dXP)
+    dx = None
+    if chained:
+        # the kept-node chain as ONE launch (csrc/dmp_nodechain.hip): dPn with its two column sums, dS = dPn Bn^T and
+        # dx = dxn + dXP Wx^T -- the partial products of dx never go through memory
+        dPn, dW2n = dXP[:, :H], None
+        dS = dead_rows_buffer((c.N, 2 * H), x.device)
+        if want_dx:
+            dx = _dx_buffer(c, x.device)
+        dbn, db2n = node_chain_bwd(dxn, H1n, dXP[:, H:], chain_panels[1], c.residual, c.slope, nd.tiles, dPn, dS, dx)
+    else:
+        dPn, dbn, db2n, dW2n = _node_out_bwd(c, dxn, H1n, dXP, not one_launch, kernel)
+        dS, dxU = _node_dS(c, dPn, dXP, dxn, want_dx)
+    if one_launch:   # the three node-side weight gradients share one launch
+        (dW2n, dBn, dWx), db2 = _node_wgrads(c, [(dxn, H1n), (S, dPn), (x, dXP)])
+        db2n = db2n if db2 is None else db2
+    else:
+        dBn = _wgrad(S, dPn, kernel)                                         # [2H,H]
+        dWx = _wgrad(x, dXP, kernel)                                         # [H,3H] = [dA_n | dPd | dPs]
+    if want_dx and not chained:
+        dx = _node_dx(c, dxn, dXP, dxU)
+    return dBn, dbn, dWx, dW2n, db2n, dS, dx
+
+
+def _l0_node_sum_products(c, tables, S0, dPn):
+    """Codes variant: S = [S0_in W0 | S0_out W0] was never built: X[h] = S0_h^T dPn per table (N rows, K columns) carries both
+    dBn_h = W0^T X[h] and the segment sums' part of the embedding gradient, sum_h X[h] Bn_h^T (no dS either) -> ``Xn`` [2, TK, H]."""
+    l0, nd, H = c.l0, c.nd, c.H
+    K0, Kp = l0.K, l0.enc.size(1)
+    Xn = (torch.empty if l0_tables_full(l0, tables, c.W0) else torch.zeros)((2, c.W0.size(0), H), dtype=torch.float32, device=dPn.device)
+    xjobs = [(S0[n0:n1, h * Kp:h * Kp + K0], dPn[n0:n1], Xn[h, t * K0:(t + 1) * K0],
+              nd.mask[n0 // 32:] if nd is not None else None) for t, _, (n0, n1) in tables if n1 > n0 for h in (0, 1)]
+    if 0 < len(xjobs) <= 4 and dPn.stride(1) == 1 and dPn.stride(0) % 2 == 0 and dPn.data_ptr() % 8 == 0:
+        smallk_atb_jobs(xjobs, H)          # both tables x both halves: one launch
+        return Xn
+    for t, _, (n0, n1) in (tables if xjobs else []):
+        if n1 > n0:
+            for h in (0, 1):
+                if nd is not None:     # (dPn's rows of the dead nodes were not written: masked out)
+                    smallk_atb_cols(S0[n0:n1, h * Kp:h * Kp + K0], dPn[n0:n1], None, Xn[h, t * K0:(t + 1) * K0].unsqueeze(0), H,
+                                    mask=nd.mask[n0 // 32:])
+                else:
+                    smallk_atb(S0[n0:n1, h * Kp:h * Kp + K0], dPn[n0:n1], out=Xn[h, t * K0:(t + 1) * K0])
+    return Xn
+
+
+def _l0_node_code_products(c, dXP, dxn):
+    """Codes variant with node codes: x = venc WV0:  x^T dXP = WV0^T (venc^T dXP)  and  venc^T dx = venc^T dxn + (venc^T dXP) Wx^T
+    -- N-row passes on K columns instead of two [N,H] x [H,3H] products and the three-block weight gradient -> ``Yn``
+    [3 (or 4: with the residual's venc^T dxn), TVK, H]."""
+    l0, nd, H, N = c.l0, c.nd, c.H, c.N
+    VK, TVK = l0.VK, c.WV0.size(0)
+    vfull = all(n1 > n0 for _, (n0, n1) in l0.vtables(N)) and len(l0.vtables(N)) * VK == TVK
+    Yn = (torch.empty if vfull else torch.zeros)((4 if c.residual else 3, TVK, H), dtype=torch.float32, device=dXP.device)
+    vmask = l0.venc_mask
+    for t, (n0, n1) in l0.vtables(N):
+        # (the packed node codes carry the node gate: a gated-out node's code row is all zeros)
+        # (one table over all nodes under the node gate: the kept nodes' list -- a node outside it has a zero code row)
+        klist = nd.rows if (nd is not None and n0 == 0 and n1 == N) else None
+        smallk_atb_cols(l0.venc[n0:n1, :VK], dXP[n0:n1], dxn[n0:n1] if c.residual else None,
+                        Yn[:, t * VK:(t + 1) * VK], H,
+                        mask=vmask[n0 // 32:] if (klist is None and vmask is not None and n0 % 32 == 0) else None, rows=klist)
+    return Yn
+
+
+def _node_bwd_codes(c, tables, S0, x, H1n, dxn, dXP, want_dx):
+    """Stage, codes variant: the node side backward of a first layer on the label codes -> ``(dbn, dWx, dW2n, db2n, Xn, Yn, dx)``:
+    dPn with the bias gradients, the K-column products in place of dS / dBn (``Xn``) and, with node codes, of dWx (``Yn``: then
+    ``dWx`` is None here), the remaining weight gradients, dx."""
+    vcodes = c.l0.venc is not None
+    one_launch, kernel = _node_one_launch(c, x, None, H1n, dxn, dXP), atb_ok(x, dXP)
+    dPn, dbn, db2n, dW2n = _node_out_bwd(c, dxn, H1n, dXP, not one_launch or vcodes, kernel)
+    Xn = _l0_node_sum_products(c, tables, S0, dPn)
+    Yn = dWx = None
+    if vcodes:
+        Yn = _l0_node_code_products(c, dXP, dxn)
+    elif one_launch:
+        (dW2n, dWx), db2 = _node_wgrads(c, [(dxn, H1n), (x, dXP)])
+        db2n = db2n if db2 is None else db2
+    else:
+        dWx = _wgrad(x, dXP, kernel)
+    return dbn, dWx, dW2n, db2n, Xn, Yn, (_node_dx(c, dxn, dXP, None) if want_dx else None)
+
+
+def _edge_input_grad(c, z, dG, dS, dzn, lazy, dWes, typed):
+    """Stage, rows variant: the edge input gradient -- residual + seg_sum2 backward + GEMM, accumulated in place -> ``(dz, dWes)``
+    (``dWes`` None on entry: ``_edge_first_wgrad`` left it to ``bwd_z_w``'s launch here).
+    The input gradient of an edge under a zero of a gate that wiped the rep-net's input rows is multiplied by that zero further
+    down: not computed.  After the first layer (``inner`` bit 1) its reader is the layer before, which leaves those rows out; the
+    first layer hands zeros to whoever made the rows."""
+    ix, coef, H, e_gate, Wes, nd = c.index, c.coef, c.H, c.e_gate, c.Wes, c.nd
+    if not typed:
+        dz = ops.gather_select_raw(dS, ix.dst32, ix.rev8, H, None, -1.0, 1.0, base=dzn if c.residual else None)
+        dz.addmm_(dG, Wes.t())
+        return dz, dWes
+    dead_dz = (("leave" if (c.inner & 2) else "zero") if dead_edge_rows(ix, H, e_gate) else None)
+    dst_m = None if nd is None else nd.sel[2]      # (dS's rows of the dead nodes were not written: read as zeros)
+    base = None if not c.residual else (lazy[0] if lazy is not None else dzn)
+    base_map = lazy[1] if (lazy is not None and c.residual) else None
+    if dWes is None:
+        both = bwd_z_w(dG, z, Wes, dS, base, coef, ix, c.WesT, base_map=base_map, gate=e_gate, dead_rows=dead_dz, dst=dst_m)
+        if both is not None:
+            return both
+        dWes = atb_typed(z, dG, coef, ix, gate=e_gate)
+    return bwd_z_typed(dG, dG.stride(0), Wes, dS, base, coef, ix, c.WesT, base_map=base_map, gate=e_gate, dead_rows=dead_dz,
+                       dst=dst_m), dWes
+
+
+def _l0_final_products(c, XX, Xn, Yn, dWx):
+    """Stage, codes variant, after the reductions of the stages before have run: ONE launch -> ``(dBn, dWx, dWes, dW0, dWV0)``.
+    dWes = W0^T (enc^T [dPre | c dPre]);  dBn_h = W0^T X_h;  enc^T dz = (enc^T [dPre | c dPre]) [A | B]^T + sum_h X_h Bn_h^T
+    (+ enc^T dzn);  with node codes dWx = WV0^T (venc^T dXP) block by block and venc^T dx = sum_b Y_b Wx_b^T (+ venc^T dxn)."""
+    H, W0, WV0, Bn, Wx, dev = c.H, c.W0, c.WV0, c.Bn, c.Wx, XX.device
+    dWes = torch.empty((H, 2 * H), dtype=torch.float32, device=dev)
+    dBn = torch.empty((2 * H, H), dtype=torch.float32, device=dev)
+    dW0 = torch.empty((W0.size(0), H), dtype=torch.float32, device=dev)
+    dWV0 = None
+    jobs = [(dWes, [(W0, True, XX[:, :2 * H], False)], None),
+            (dBn[:H], [(W0, True, Xn[0], False)], None), (dBn[H:], [(W0, True, Xn[1], False)], None),
+            (dW0, [(XX[:, :2 * H], False, c.Wes, True), (Xn[0], False, Bn[:H], True), (Xn[1], False, Bn[H:], True)],
+             XX[:, 2 * H:] if c.residual else None)]
+    if Yn is not None:
+        dWx = torch.empty((H, 3 * H), dtype=torch.float32, device=dev)
+        dWV0 = torch.empty((WV0.size(0), H), dtype=torch.float32, device=dev)
+        for b3 in range(3):
+            jobs.append((dWx[:, b3 * H:(b3 + 1) * H], [(WV0, True, Yn[b3], False)], None))
+        jobs.append((dWV0, [(Yn[b3], False, Wx[:, b3 * H:(b3 + 1) * H], True) for b3 in range(3)], Yn[3] if c.residual else None))
+    small_gemm_jobs(jobs)
+    return dBn, dWx, dWes, dW0, dWV0
+
+
 class _FusedDMPLayer(torch.autograd.Function):
-    """One DMPNN layer + gate + residual over the folded weights of ``fold_layers``."""
+    """One DMPNN layer + gate + residual over the folded weights of ``fold_layers``: each pass a short list of the stages above."""
 
     @staticmethod
     def forward(ctx, index, coef, residual, x, z, v_gate, e_gate, Bn, bn, Wx, Wes, be, nW2, nb2, eW2, eb2,
@@ -1820,592 +2530,63 @@ class _FusedDMPLayer(torch.autograd.Function):
         ``vpool`` / ``epool`` (``ops.PoolIndex`` over the node / edge rows; the LAST layer of a rep-net whose outputs
         feed sum / mean pooling heads): two more outputs, the per-graph sums of ``xn`` / ``zn`` ([G, H]; edges with a flag
         [G, 2H] = [non-reversed | reversed]).  A gradient that arrives ONLY through the edge sums is never expanded to
-        [E, H]: every row of a graph has the same gradient vector, see ``backward``."""
+        [E, H]: every row of a graph has the same gradient vector, see ``_grad_seeds``."""
         _lib.require_gpu(x, z)
         H = Bn.size(1)
         x, z = x.contiguous(), z.contiguous()
-        Bn, Wx, Wes = Bn.contiguous(), Wx.contiguous(), Wes.contiguous()
-        N = index.num_nodes
-        # ---- the nodes a 0 / 1 node gate keeps (``node_rows``): a node under a zero of a gate whose maker wiped the input rows
-        # is a zero row in every layer, so its aggregate, its projections, its update and all of its gradient rows are dead --
-        # the node side runs on the kept nodes' tiles, the edge kernels read a dead node's (unwritten) rows as zeros
-        from . import side      # (index builds issued ahead on the side stream, dmpnn.prefetch_joint_indexes: wait for a stage at its first use)
-        side.wait("nodes")
-        nd = node_rows(index, v_gate, H) if kept_node_path(index, H, v_gate, l0) else None
+        c = _LayerCall(index=index, coef=coef, residual=residual, H=H, N=index.num_nodes, slope=slope, inner=int(inner),
+                       v_gate=v_gate, e_gate=e_gate, Bn=Bn.contiguous(), bn=bn, Wx=Wx.contiguous(), Wes=Wes.contiguous(), be=be,
+                       nW2=nW2, nb2=nb2, eW2=eW2, eb2=eb2, WesT=WesT, nW2t=nW2t, eW2t=eW2t, l0=l0,
+                       W0=None if l0 is None else W0.detach(), WV0=None if (l0 is None or WV0 is None) else WV0.detach(),
+                       nd=_kept_nodes(index, H, v_gate, l0), vpool=vpool, epool=epool)
         # ---- node side (dmpnn.py:113,121,125 + fn.sum + 129-140)
-        S0 = M0 = tables = None
-        chained, chain_panels = False, None
-        if l0 is not None:     # sum of z over a node's edges = (sum of the label codes) W0
-            enc0, K0 = l0.enc, l0.K
-            tables = l0.tables(z.size(0), N)
-            if nd is not None and enc0.size(1) % 4 == 0:
-                # (the code sums of the kept nodes only: every reader -- the node pass over the kept list, the backward's masked
-                # K-column products -- leaves the dead nodes' rows out)
-                S0 = ops.seg_sum_raw(enc0, index.in_ptr, index.in_ent, N, None, True, -1.0, 1.0,
-                                     out=dead_rows_buffer((N, 2 * enc0.size(1)), z.device), rows=nd.rows, tag="seg_sum2_codes")
-            else:
-                S0 = ops.seg_sum_raw(enc0, index.in_ptr, index.in_ent, N, None, True, -1.0, 1.0)    # [N, 2 Kpad] = [in | out]
-            # S = [S0_in W0 | S0_out W0] is never built:  S Bn = S0_in (W0 Bn_in) + S0_out (W0 Bn_out), two K-column products
-            Kp = enc0.size(1)
-            vcodes_f = l0.venc is not None
-            node_pass = (vcodes_f and H in MFMA_WIDTHS and l0.VK + 2 * K0 <= L0_NODE_MAX_COLS and W0.size(0) // K0 <= 2)
-            # the parameter-only products of this layer in ONE launch: W0 Bn_in, W0 Bn_out, W0 [A | B], WV0 Wx
-            TK = W0.size(0)
-            M0 = torch.empty((TK, 2 * H), dtype=torch.float32, device=z.device)
-            jobs = [(M0, [(W0, False, Wes, False)], None)]
-            if node_pass:
-                # ... written straight into the node pass's packed matrix, one per embedding table: rows 0 .. VK-1 = WV0 Wx (three
-                # column blocks), then K0 rows W0 Bn_in and K0 rows W0 Bn_out in the first block; zeros elsewhere
-                VK = l0.VK
-                WP = torch.zeros((TK // K0, L0_NODE_MAX_COLS, 3 * H), dtype=torch.float32, device=z.device)
-                for t in range(TK // K0):
-                    WVt = WV0 if WV0.size(0) == VK else WV0[t * VK:(t + 1) * VK]
-                    jobs += [(WP[t, :VK], [(WVt, False, Wx, False)], None),
-                             (WP[t, VK:VK + K0, :H], [(W0[t * K0:(t + 1) * K0], False, Bn[:H], False)], None),
-                             (WP[t, VK + K0:VK + 2 * K0, :H], [(W0[t * K0:(t + 1) * K0], False, Bn[H:], False)], None)]
-            else:
-                WB = torch.empty((2, TK, H), dtype=torch.float32, device=z.device)
-                jobs += [(WB[0], [(W0, False, Bn[:H], False)], None), (WB[1], [(W0, False, Bn[H:], False)], None)]
-                if vcodes_f:
-                    MV = torch.empty((WV0.size(0), 3 * H), dtype=torch.float32, device=z.device)
-                    jobs.append((MV, [(WV0, False, Wx, False)], None))
-            small_gemm_jobs(jobs)
-            if node_pass:
-                # the whole node side before the second Linear in ONE pass over the codes: H1n and the two projection blocks
-                # (the kept nodes' H1n rows only; a dead node's projection rows are zeros)
-                H1n = dead_rows_buffer((N, H), z.device) if nd is not None else torch.empty((N, H), dtype=torch.float32, device=z.device)
-                PX = torch.empty((N, 2 * H), dtype=torch.float32, device=z.device)
-                for t, _, (n0, n1) in tables:
-                    if n1 > n0 and (nd is None or n1 <= nd.prefix):      # (no gate, or the pattern's nodes -- all kept: every row)
-                        l0_node_fwd(l0.venc, VK, S0, K0, Kp, WP[t], bn, slope, None, n0, n1, H, H1n, PX)
-                    elif n1 > n0:
-                        l0_node_fwd(l0.venc, VK, S0, K0, Kp, WP[t], bn, slope, nd.mask, n0, n1, H, H1n, PX, rows=nd.rows,
-                                    q_begin=min(nd.prefix, n0))
-            else:
-                SB = torch.empty((N, H), dtype=torch.float32, device=z.device)
-                for t, _, (n0, n1) in tables:      # (N-row products: the small-product kernel is built for a few hundred rows)
-                    if n1 > n0:
-                        torch.mm(S0[n0:n1, :K0], WB[0, t * K0:(t + 1) * K0], out=SB[n0:n1])
-                        SB[n0:n1].addmm_(S0[n0:n1, Kp:Kp + K0], WB[1, t * K0:(t + 1) * K0])
-            S = None
+        S = S0 = M0 = tables = xn = chain_panels = None
+        if l0 is not None:
+            S0, M0, tables, H1n, P, ldp = _node_first_codes(c, x, z)
         else:
-            # (input rows under a zero of a gate whose maker wiped them -- ``zero_rows_gate`` -- are zeros: not fetched)
-            side.wait("keepcsr")
-            kc = keep_in_csr(index, e_gate) if zero_rows_gate(e_gate) else None
-            if kc is not None and nd is not None:   # ... and over the kept NODES' rows only: the others' aggregates are dead
-                # (measured twice -- before and after the remap fix of finding (u): row pointers by list position,
-                # ``NodeRows.kept_incidence(in_only=True)``, one dependent load less per row group, leave the launch where it is)
-                S = ops.seg_sum_raw(z, kc[0], kc[1], N, None, True, -1.0, 1.0, out=dead_rows_buffer((N, 2 * H), z.device), rows=nd.rows)
-            elif kc is not None:      # the CSR over the kept edges: the plain kernel, no entries of skipped rows in its stream
-                S = ops.seg_sum_raw(z, kc[0], kc[1], N, None, True, -1.0, 1.0)
-            else:
-                S = ops.seg_sum_raw(z, index.in_ptr, index.in_ent, N, e_gate.reshape(-1) if zero_rows_gate(e_gate) else None, True, -1.0, 1.0)
-            if nd is None:
-                SB = S @ Bn
-        if l0 is None and nd is not None:
-            # the node side on the kept nodes' tiles (the tile kernel with a plain panel, 128-wide block products; independent
-            # products share a launch): H1n = act(x Wx0 + S_in Bn_in + S_out Bn_out + bn) as two partial products + a third
-            # that adds them up, the two gathered projection blocks, xn = x + (H1n W2^T + b2) -- nothing is read or written
-            # for the other nodes
-            T = nd.tiles
-            H1n = dead_rows_buffer((N, H), z.device)
-            chained = node_chain_ok(H, x, S, Bn, Wx, nW2)
-            if chained:
-                # ... as ONE launch: the rows stay in the workgroup, the six panels stream through LDS (csrc/dmp_nodechain.hip) --
-                # the partial products x Wx0 + bn and S_in Bn_in never go through memory
-                PX = dead_rows_buffer((N, 2 * H), z.device)      # [P_dst | P_src]
-                # (an INNER layer's xn: the dead rows stay unwritten; the last layer's rows go to the caller: zeros there)
-                xn = dead_rows_buffer((N, H), z.device) if (inner & 1) else torch.zeros((N, H), dtype=torch.float32, device=z.device)
-                chain_panels = node_chain_panels(Bn, Wx, nW2)    # (both passes' panels: one launch per layer and step)
-                node_chain_fwd(x, S, chain_panels[0], bn, nb2, residual, slope, T, H1n, PX, xn)
-            else:
-                XP = dead_rows_buffer((N, 3 * H), z.device)          # [x Wx0 + bn (a partial) | P_dst | P_src]
-                T1 = dead_rows_buffer((N, H), z.device)
-                typed_jobs([dict(a=x, W=Wx[:, :H], bias=bn, out=XP[:, :H]), dict(a=S[:, :H], W=Bn[:H], out=T1),
-                            dict(a=x, W=Wx[:, H:2 * H], out=XP[:, H:2 * H]), dict(a=x, W=Wx[:, 2 * H:], out=XP[:, 2 * H:])], T)
-                out_fwd_typed(S[:, H:], Bn[H:], None, XP[:, :H], T, out=H1n, slope=slope, prev2=T1)
-        elif l0 is not None and node_pass:
-            pass
-        elif l0 is not None and l0.venc is not None:     # x Wx = venc (WV0 Wx): three column blocks of K-column products
-            VK = l0.VK
-            XP = torch.empty((N, 3 * H), dtype=torch.float32, device=z.device)
-            for t, (n0, n1) in l0.vtables(N):
-                smallk_embed(l0.venc[n0:n1, :VK], MV[t * VK:(t + 1) * VK], None, XP[n0:n1], H)
-        else:
-            XP = x @ Wx
-        if (l0 is not None and node_pass) or chained:
-            PXr, ldpx = PX, 2 * H                # the gathered projections [P_dst | P_src]
-        else:
-            PXr, ldpx = XP[:, H:], 3 * H
-            if l0 is not None or nd is None:
-                H1n = add_bias_relu_(SB, XP[:, :H], bn, slope)
-        if chained:
-            pass
-        elif nd is not None:
-            # (an INNER layer's xn is read by the next layer of this rep-net only, under the same gate: the dead rows stay
-            # unwritten; the last layer's rows go to the caller: zeros there)
-            xn = dead_rows_buffer((N, H), z.device) if (inner & 1) else torch.zeros((N, H), dtype=torch.float32, device=z.device)
-            if nW2t is not None:
-                out_fwd_typed(H1n, nW2t, nb2, x if residual else None, nd.tiles, out=xn)
-            else:
-                out_fwd_typed(H1n, nW2, nb2, x if residual else None, nd.tiles, out=xn, w_in_out=False)
-        elif onepanel_ok(H):   # Linear + gate + residual in one fused MFMA kernel, as on the edge side
-            xn = out_fwd_mfma(H1n, nW2, nb2, v_gate, x if residual else None, nW2t)
-        else:
-            xn = gate_residual(x if residual else None, torch.addmm(nb2, H1n, nW2.t()), v_gate)
+            S, H1n, P, ldp, xn, chain_panels = _node_first_rows(c, x, z)
+        if xn is None:
+            xn = _node_out(c, x, H1n)
         # ---- edge side (dmpnn.py:112,120,124 + 142-156)
         sums_only = epool is not None and not edge_rows
-        zn = None
-        side.wait("erows" if l0 is not None else "tiles")      # (a layer on the label codes needs the tiles only for its second Linear)
-        dead_gate = e_gate if dead_h1_rows(index, H, e_gate) else None     # (the two producers of H1e leave its dead rows out)
-        dead_in = dead_gate is not None and dead_edge_rows(index, H, e_gate)
-        # the one-launch edge MLP stands exactly where the route below is edge_fwd_typed + out_fwd_typed over the kept edges' tiles
-        # (dead == 3 with live_tiles and the folded W2^T): a gated INNER layer whose edge rows are wanted, with its residual
-        mlp_tiles = None
-        if (l0 is None and dead_in and not sums_only and residual and eW2t is not None and (inner & 1)
-                and edge_mlp_fwd_ok(H, z, PXr, eW2t)):
-            mlp_tiles = live_tiles(index, coef, e_gate)
         if l0 is not None:
-            H1e = dead_rows_buffer((z.size(0), H), z.device) if dead_gate is not None else torch.empty((z.size(0), H), dtype=torch.float32, device=z.device)
-            # the one-launch edge MLP stands exactly where the route is l0_edge_fwd per table + out_fwd_typed_codes (below): over the
-            # kept edges' tiles under the gates (whose zero rows are dead rows of H1e: the per-table launches leave them out as well,
-            # where their mask starts at a whole word), over the identity tiles without a gate
-            l0_tiles = None
-            if (not sums_only and residual and eW2t is not None and getattr(l0, "z_from_codes", False)
-                    and out_codes_ok(H1e, l0.enc, l0.K, W0[-l0.K:])
-                    and l0_edge_mlp_ok(H, K0, W0.size(0) // K0, enc0, PXr, eW2t, l0.z_head)):
-                if dead_in and (inner & 1):
-                    side.wait("tiles")
-                    lt = live_tiles(index, coef, e_gate)
-                    if lt is not None:
-                        l0_tiles = ascending_tiles(e_gate) or lt
-                elif e_gate is None:
-                    # (212 against 275 us for the launches of their own; the first build was time-neutral here: docs/HISTORY.md (oo))
-                    l0_tiles = identity_tiles(H1e.size(0), H1e.device)
-            if l0_tiles is not None:
-                # both Linears as ONE launch: H1e goes from the first to the second on the chip, the code rows are fetched once
-                # (through the second Linear's wrapper, as every E-row Linear + residual launch goes: it fills H1e on the way)
-                zn = out_fwd_typed_codes(H1e, eW2t, eb2, l0.enc, l0.K, W0[-l0.K:], l0_tiles, prev=l0.z_head, row0=l0.z_head.size(0),
-                                         first=dict(M=M0, tables=W0.size(0) // K0, split=l0.esplit, P=PXr, ldp=ldpx, bias=be, coef=coef,
-                                                    index=index, slope=slope))
-            else:
-                for t, rows, _ in tables:
-                    if rows[1] > rows[0]:
-                        l0_edge_fwd(enc0, K0, M0[t * K0:(t + 1) * K0], PXr, ldpx, be, coef, index, slope, rows, H1e,
-                                    mask=gate_row_mask(dead_gate) if dead_gate is not None else None)
-        elif mlp_tiles is not None:
-            # both Linears over the kept edges' class tiles as ONE launch: H1e goes from the first to the second on the chip
-            # (through the second Linear's wrapper, as every E-row Linear + residual launch goes: it fills H1e on the way)
-            H1e = dead_rows_buffer((z.size(0), H), z.device)
-            zn = out_fwd_typed(H1e, eW2t, eb2, z, mlp_tiles,
-                               first=dict(z=z, Wes=Wes, P=PXr, ldp=ldpx, bias=be, coef=coef, index=index, slope=slope,
-                                          sel=None if nd is None else nd.sel))
-        elif typed_ok(index, H):
-            # (under ``nd`` the projection rows of the dead nodes were never written: their selectors read as zeros)
-            H1e = edge_fwd_typed(z, Wes, PXr, ldpx, be, coef, index, slope, dead_gate=dead_gate, sel=None if nd is None else nd.sel)
-        elif mfma_ok(index, H):
-            H1e = edge_fwd_mfma(z, Wes, PXr, ldpx, be, coef, index, slope)
+            H1e, zn = _edge_first_codes(c, z, M0, tables, P, ldp, sums_only)
         else:
-            G = z @ Wes
-            H1e = edge_combine_raw(G, 2 * H, PXr, ldpx, be, coef, index, H, relu=True, slope=slope)
-            del G
-            if not sums_only:
-                Oe = torch.addmm(eb2, H1e, eW2.t())
-                zn = gate_residual(z if residual else None, Oe, e_gate)
+            H1e, zn = _edge_first_rows(c, z, P, ldp, sums_only)
         if zn is None and not sums_only:
-            # a gate whose maker wiped the rep-net's input rows (zero_rows_gate): z's rows under its zeros are zeros -- not
-            # fetched; as an INNER layer of a rep-net (``inner``: the next layer of the same rep-net, under the same gate,
-            # is the only reader of zn) the output's zero rows are not stored either
-            dead = (3 if (inner & 1) else 1) if dead_in else 0
-            side.wait("tiles")
-            lt = live_tiles(index, coef, e_gate) if (dead == 3 and eW2t is not None) else None
-            if lt is not None:      # nothing to write for the rows under a zero gate: the kept edges' tiles only
-                # (a plain panel needs no class: the kept edges' tiles in ascending row order -- ``ascending_tiles``)
-                tl_ = ascending_tiles(e_gate) or lt
-                if l0 is not None and residual and getattr(l0, "z_from_codes", False) and out_codes_ok(H1e, l0.enc, l0.K, W0[-l0.K:]):
-                    # the target's residual rows z = enc W0 are not in memory at all (``dmpnn.joint_rep`` did not make them): one more
-                    # k-group over their codes; the pattern's few rows (their own table) come in as the residual operand
-                    zn = out_fwd_typed_codes(H1e, eW2t, eb2, l0.enc, l0.K, W0[-l0.K:], tl_, prev=l0.z_head, row0=l0.z_head.size(0))
-                else:
-                    zn = out_fwd_typed(H1e, eW2t, eb2, l0_rows(l0, W0, z) if residual else None, tl_)
-            elif (l0 is not None and residual and e_gate is None and getattr(l0, "z_from_codes", False) and eW2t is not None
-                  and out_codes_ok(H1e, l0.enc, l0.K, W0[-l0.K:]) and identity_tiles(H1e.size(0), H1e.device) is not None):
-                # no gate at all (the all-rows step): the same launch over the identity tile list
-                zn = out_fwd_typed_codes(H1e, eW2t, eb2, l0.enc, l0.K, W0[-l0.K:], identity_tiles(H1e.size(0), H1e.device), prev=l0.z_head,
-                                         row0=l0.z_head.size(0))
-            else:
-                zn = out_fwd_mfma(H1e, eW2, eb2, e_gate, l0_rows(l0, W0, z) if residual else None, eW2t, dead_rows=dead)
-        ctx.index, ctx.coef, ctx.residual, ctx.H = index, coef, residual, H
-        ctx.v_gate, ctx.e_gate, ctx.WesT, ctx.slope = v_gate, e_gate, WesT, slope
-        ctx.vpool, ctx.epool = vpool, epool
-        ctx.inner = int(inner)
-        ctx.nd = nd
-        ctx.chain_panels = chain_panels
-        ctx.l0, ctx.l0_S0, ctx.l0_tables = l0, S0, tables
-        ctx.l0_W = None if l0 is None else (W0.detach(), None if WV0 is None else WV0.detach())
-        ctx.save_for_backward(x, z if l0 is None else None, S, H1n, H1e, Bn, Wx, Wes, nW2, eW2)
+            zn = _edge_out(c, z, H1e)
+        ctx.call, ctx.chain_panels, ctx.l0_S0, ctx.l0_tables, ctx.gcnt = c, chain_panels, S0, tables, None
+        ctx.save_for_backward(x, z if l0 is None else None, S, H1n, H1e)
         if vpool is None and epool is None:
             return xn, zn
         ctx.set_materialize_grads(False)    # a missing gradient stays None (the common case: only the sums are used)
-        vs = pool_rows(xn, vpool) if vpool is not None else None
-        if sums_only:
-            halves = 2 if epool.flag8 is not None else 1
-            G_ = epool.num_graphs
-            Q = pool_rows(H1e, epool, e_gate).view(G_ * halves, H)                      # sum of g H1 per graph (and flag)
-            cnt = pool_weight_sums(epool, e_gate)                                        # sum of g per graph (and flag)
-            ctx.gcnt = cnt                                                               # the backward's db2 needs them again
-            cnt = cnt.view(G_ * halves, 1)
-            # (z's rows under a zero of a gate whose maker wiped the input are zeros, and as an inner layer's output not even
-            # written: weight 0, not fetched)
-            zs = pool_rows(z, epool, e_gate if zero_rows_gate(e_gate) else None).view(G_ * halves, H) if residual else None
-            if Q.is_contiguous() and eW2.is_contiguous() and Q.size(0) <= SMALL_GEMM_MAX_ROWS:
-                es = torch.empty((G_ * halves, H), dtype=torch.float32, device=Q.device)  # Q W2^T + cnt b2 (+ sum of z): one launch
-                small_gemm_jobs([(es, [(Q, False, eW2, True), (cnt, False, eb2.view(1, H), False)], zs)])
-            else:
-                # (thousands of graphs: the small-product kernel is built for a few hundred rows -- 43 us at 4096 rows against
-                # 13 for a library product + one row pass)
-                es = torch.addmm(zs, Q, eW2.t()) if residual else Q @ eW2.t()
-                es.addcmul_(cnt, eb2.view(1, H))
-            # ... of which only the NON-FLAGGED half is returned ([G, H]): without the rows the backward propagates a gradient
-            # through that half only (the row map is -1 for flagged rows), so the flagged sums are not handed out as if they
-            # were differentiable (the heads mask reversed edges out and read [:, :H] anyway, basemodel.py:1545-1631)
-            es = es.view(G_, halves * H)[:, :H]
-        else:
-            es = pool_rows(zn, epool) if epool is not None else None
+        vs, es, ctx.gcnt = _pooled_outputs(c, z, xn, zn, H1e, sums_only)
         return xn, zn, vs, es
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dxn, dzn, dvs=None, des=None):
-        x, z, S, H1n, H1e, Bn, Wx, Wes, nW2, eW2 = ctx.saved_tensors
-        ix, coef, H, slope = ctx.index, ctx.coef, ctx.H, ctx.slope
-        N = ix.num_nodes
-        nd = ctx.nd       # the kept nodes of a 0 / 1 node gate (``node_rows``): every gradient row of another node is dead
-        # ---- gradients through the pooled sums (last layer).  Node side: expanded (N rows are cheap).  Edge side: if the
-        # sums are the ONLY consumer of zn, dzn[e] = T[graph of e] (zero for reversed edges) with T = des[:, :H] and
-        #   dH1 = (g (.) dzn) W2 = g[e] (T W2)[graph of e]             -> no E-row product, no [E, H] gradient tensor
-        #   dW2 = (g (.) dzn)^T H1 = T^T Q,  Q[b] = sum_{e in b} g[e] H1[e]   -> one pooled pass over H1
-        #   db2 = T^T (sum_{e in b} g[e])
-        # and the residual term of dz reads T through the row map.
-        lazy = None
-        if dvs is not None:
-            vp = ctx.vpool
-            exp = ops.gather_rows_raw(dvs.contiguous(), vp.seg32)
-            dxn = exp if dxn is None else dxn + exp
-        if des is not None:
-            ep = ctx.epool
-            if dzn is None and typed_ok(ix, H) and H1e.size(0) > 0 and des.size(1) == H:
-                # des is [G, H]: the row-less forward hands out the non-flagged sums only, or no flag splits the sums.  A
-                # [G, 2H] gradient (forward with rows, flag-split sums) may carry a flagged half: the expanded path below
-                lazy = (des.contiguous(), pool_rowmap(ep), ep)
-            else:
-                if ep.flag8 is not None and des.size(1) == H:     # the row-less forward's [G, H]: nothing flows to the flagged rows
-                    des = torch.cat([des, torch.zeros_like(des)], dim=1)
-                exp = (ops.gather_select_raw(des.contiguous(), ep.seg32, ep.flag8, H, None, 1.0, 1.0) if ep.flag8 is not None
-                       else ops.gather_rows_raw(des.contiguous(), ep.seg32))
-                dzn = exp if dzn is None else dzn + exp
-        if dxn is None:
-            dxn = torch.zeros_like(x)
-        if dzn is None and lazy is None:
-            dzn = torch.zeros_like(z)
-        dxn = dxn.contiguous()
-        dzn = dzn.contiguous() if dzn is not None else None
+        x, z, S, H1n, H1e = ctx.saved_tensors
+        c, tables = ctx.call, ctx.l0_tables
+        typed = typed_ok(c.index, c.H)
+        want_dx, want_dz = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        dxn, dzn, lazy = _grad_seeds(c, x, z, H1e, dxn, dzn, dvs, des, typed)
+        dz = dW0 = dWV0 = None
         # the parameter-gradient partials (biases, split-K weight gradients) are consumed after the layer (by the
         # unfold of fold_layers / the optimizer): their reductions run as one launch when this block is left
         with deferred_reductions():
-            # ---- edge side, down to the gathered node projections
-            mfma, typed = mfma_ok(ix, H), typed_ok(ix, H)
-            l0_XX = None     # (XX, codes) once ``bwd_h1_w`` takes the last table's code weight gradient along
-
-            def l0_tables_full():
-                # every table has edge rows and node rows: every block of the code products is written
-                return all(r[1] > r[0] and n[1] > n[0] for _, r, n in ctx.l0_tables) and len(ctx.l0_tables) * ctx.l0.K == ctx.l0_W[0].size(0)
-
-            def l0_codes_buffer(H, device):
-                # [TK, 2H or 3H]: a table without edge rows leaves its block to the zeros
-                return (torch.empty if l0_tables_full() else torch.zeros)((ctx.l0_W[0].size(0), (3 if ctx.residual else 2) * H),
-                                                                            dtype=torch.float32, device=device)
-
-            def l0_codes_block(H, device, walked):
-                if not h1w_codes_ok(ctx.l0, ctx.l0_tables or (), walked):
-                    return None
-                t, rows, _ = ctx.l0_tables[-1]
-                XX, K0 = l0_codes_buffer(H, device), ctx.l0.K
-                return XX, dict(enc=ctx.l0.enc, K=K0, coef_e=ix.edge_select(coef)[2], rows=rows, residual=ctx.residual, out=XX[t * K0:(t + 1) * K0])
-
-            if lazy is not None:
-                T, emap, ep = lazy
-                if H % 4 == 0 and H <= 256:
-                    # (dPre's rows under a zero of a 0 / 1 gate: every reader below leaves them out -- the kept incidence sums,
-                    # the class-tile kernels over the kept edges' tiles)
-                    skip = ctx.l0 is None and nd is not None and USE_PLAIN_ATB and dead_edge_rows(ix, H, ctx.e_gate, coef)
-                    dG, dbe, Q = pool_relu_bwd(T @ eW2, emap, ctx.e_gate, H1e, ep, slope, skip_dead=skip)       # dG is dPre; one pass over H1e
-                    Q = Q[:, :H]
-                else:
-                    dG, dbe = relu_bwd_gathered_colsum(T @ eW2, emap, ctx.e_gate, H1e, slope)
-                    Q = pool_rows(H1e, ep, ctx.e_gate)[:, :H]
-                dW2e = T.t() @ Q
-                # gated row counts per graph
-                gcnt = getattr(ctx, "gcnt", None)
-                if gcnt is None:
-                    gcnt = pool_weight_sums(ep, ctx.e_gate)
-                db2e = gcnt[:, 0] @ T
-            elif typed:
-                # the gate is applied inside the two consumers of dO = gate * dzn (no [E,H] pass of its own)
-                if binary_gate_mask(ctx.e_gate) is not None:
-                    # a 0 / 1 gate: bwd_h1 hands out sum_e g_e dzn[e] (db2) from the rows it fetches anyway, and the weight
-                    # gradient runs ungated over the masked-in rows on the bf16 pipe
-                    # (dPre's zero rows are not stored: the class-tile kernels, the scatter-add and the layer-0 products below
-                    # leave them out)
-                    skip = (USE_MASKED_SUMS and dead_h1_rows(ix, H, ctx.e_gate)
-                            and (ctx.l0 is None or getattr(ctx.l0, "enc_mask", None) is not None))
-                    lt = live_tiles(ix, coef, ctx.e_gate) if skip else None
-                    if lt is not None and h1w_ok(dzn, H1e, H):
-                        # both products of the second Linear's backward from ONE pass over dO and H1 (csrc/dmp_h1w.hip) -- and, in
-                        # the first layer, the target table's code weight gradient over the same kept rows (``l0_bwd_w``'s launch)
-                        l0_XX = l0_codes_block(H, dzn.device, "kept")
-                        dG, dbe, db2e, dW2e = bwd_h1_w(dzn, eW2, H1e, ascending_tiles(ctx.e_gate) or lt, slope, codes=l0_XX and l0_XX[1])[:4]
-                    elif lt is not None:      # over the kept edges' tiles only
-                        dG, dbe, db2e = bwd_h1_typed(dzn, eW2, H1e, ascending_tiles(ctx.e_gate) or lt, slope)
-                        # dO^T H1 over the kept edges' tiles: the class-tile weight-gradient kernel's first half (its class-scaled
-                        # second half costs no further products) -- no tiles' worth of zero rows in between
-                        dW2e = atb_typed(dzn, H1e, coef, ix, gate=ctx.e_gate, plain=True)
-                    else:
-                        dG, dbe, db2e = bwd_h1_mfma(dzn, eW2, H1e, coef, ix, both_halves=False, gate=ctx.e_gate, slope=slope, rows_colsum=True,
-                                                    skip_dead_stores=skip)
-                        dW2e = atb_rows(dzn, H1e, ctx.e_gate, colsum=False)[0]
-                else:
-                    it = identity_tiles(dzn.size(0), dzn.device) if (ctx.e_gate is None and h1w_ok(dzn, H1e, H)) else None
-                    if it is not None:
-                        # no gate at all (a model without a filter net: the reference's one-label datasets): every row is live --
-                        # both products of the second Linear's backward in one launch over the identity tile list
-                        l0_XX = l0_codes_block(H, dzn.device, "all")
-                        dG, dbe, db2e, dW2e = bwd_h1_w(dzn, eW2, H1e, it, slope, codes=l0_XX and l0_XX[1])[:4]
-                    else:
-                        dW2e, db2e = atb_rows(dzn, H1e, ctx.e_gate)
-                        dG, dbe = bwd_h1_mfma(dzn, eW2, H1e, coef, ix, both_halves=False, gate=ctx.e_gate, slope=slope)  # dG is dPre
+            dG, dbe, dW2e, db2e, l0_XX = _edge_out_bwd(c, tables, H1e, dzn, lazy, ctx.gcnt, typed)
+            dXP = _endpoint_sums(c, dG, typed, x.device)
+            if c.l0 is not None:
+                XX = _l0_edge_code_products(c, tables, dG, dzn, l0_XX)
+                dbn, dWx, dW2n, db2n, Xn, Yn, dx = _node_bwd_codes(c, tables, ctx.l0_S0, x, H1n, dxn, dXP, want_dx)
             else:
-                dOe, db2e = scale_rows_colsum(dzn, ctx.e_gate)
-                dW2e = atb(dOe, H1e)
-                if mfma:
-                    dG, dbe = bwd_h1_mfma(dOe, eW2, H1e, coef, ix, both_halves=True, slope=slope)     # dG[:, :H] is dPre
-                else:
-                    dH1e = dOe @ eW2
-                    dG, dbe = relu_bwd_g_colsum(dH1e, H1e, coef, ix.dst32, slope)
-                    del dH1e
-            # [dPn | dP]: written in place, no concatenation (under ``nd``: the kept nodes' rows only)
-            dXP = dead_rows_buffer((N, 3 * H), x.device) if nd is not None else torch.empty((N, 3 * H), dtype=torch.float32, device=x.device)
-            # dPre into both endpoints' rows: the backward scatter-add (dPre's rows under a zero edge gate are zeros: not fetched)
-            sums_masked = typed and USE_MASKED_SUMS and has_row_mask(ctx.e_gate)
-            # (... and the rows of the dead nodes are neither summed nor stored)
-            if kept_incidence_sums(ix, H, ctx.e_gate, nd is not None):
-                # every kept node's two sums over its KEPT edges (the incidence CSR over the kept edges, a row per kept node):
-                # the plain segment-sum kernel, ascending edge id -- an edge row without a kept endpoint is never fetched
-                kp, ke = nd.kept_incidence(ix, ctx.e_gate)
-                ops.seg_sum_raw(dG[:, :H], kp, ke, N, None, True, 1.0, -1.0, out=dXP[:, H:], rows=nd.rows, ptr_by_pos=True, tag="seg_sum2_kept_inc",
-                                incidence=True)
-            else:
-                nodes = (nd.mask, nd.sel[:2]) if (nd is not None and sums_masked and ops.graph_seg_ok(ix, dG[:, :H], H, dXP[:, H:])) else None
-                ops.endpoint_sums(dG[:, :H], ix, out=dXP[:, H:], mask=gate_row_mask(ctx.e_gate) if sums_masked else None,
-                                  gate=ctx.e_gate if sums_masked else None, nodes=nodes)
-            l0, tables = ctx.l0, ctx.l0_tables
-            vcodes = l0 is not None and l0.venc is not None
-            if l0 is not None:   # z = enc W0: one pass over dPre (and the residual gradient) on the K-column factor
-                W0, WV0 = ctx.l0_W
-                K0, TK = l0.K, W0.size(0)
-                full = l0_tables_full()
-                # (the last table's block may be there already: ``bwd_h1_w(codes=...)`` above made it in its launch)
-                XX = l0_XX[0] if l0_XX is not None else l0_codes_buffer(H, dG.device)
-                for t, rows, _ in (tables[:-1] if l0_XX is not None else tables):
-                    if rows[1] > rows[0]:
-                        # (the rows to add: those with a non-zero code row -- or, where dPre's rows under a zero gate were not
-                        # stored, the rows the gate keeps: the same list the forward walked; a kept row with a zero code adds zeros)
-                        l0_bwd_w(l0.enc, K0, ix.edge_select(coef)[2], dG, dzn if ctx.residual else None, rows, XX[t * K0:(t + 1) * K0],
-                                 mask=(gate_row_mask(ctx.e_gate) if (getattr(l0, "enc_mask", None) is not None and binary_gate_mask(ctx.e_gate) is not None)
-                                       else getattr(l0, "enc_mask", None)))
-                dWes = None
-            else:
-                # (dG = dPre has zero rows under a zero edge gate, whichever kernel made it: the typed kernels skip those edges)
-                # (with the input gradient still to come -- ``dz`` below, over the same tile list -- both products of dPre run in ONE
-                # launch there, ``bwd_z_w``: decided here, made there)
-                fuse_dzw = bool(typed and ctx.needs_input_grad[4] and H == 128 and
-                                (ctx.e_gate is None or dead_edge_rows(ix, H, ctx.e_gate, coef)))
-                dWes = None if fuse_dzw else (atb_typed(z, dG, coef, ix, gate=ctx.e_gate) if typed else atb(z, dG))   # [H,2H] = [dA_e | dB_e]
-            # ---- node side
-            wg = (lambda a, b: atb_rows(a, b, colsum=False)[0]) if atb_ok(x, dXP) else atb   # MFMA kernel or library GEMMs
-            one_launch = onepanel_ok(H) and atb_ok(dxn, H1n) and atb_ok(x, dXP) and (l0 is not None or atb_ok(S, dXP))
-            if nd is not None and not (one_launch and binary_gate_mask(ctx.v_gate) is not None):
-                raise _lib.DmpError("fused layer backward: the kept-node path needs the masked weight-gradient launch")
-            chained = (nd is not None and l0 is None and ctx.chain_panels is not None
-                       and node_chain_ok(H, dxn, H1n, dXP))
-            dx = None
-            if chained:
-                # the kept-node chain as ONE launch (csrc/dmp_nodechain.hip): dPn with its two column sums, dS = dPn Bn^T and
-                # dx = dxn + dXP Wx^T -- the partial products of dx never go through memory.  A dead node's dx row: left unwritten
-                # where the layer before is the only reader (``inner`` bit 1), zeros for whoever made the first layer's rows
-                dPn = dXP[:, :H]
-                dS = dead_rows_buffer((N, 2 * H), x.device)
-                if ctx.needs_input_grad[3]:
-                    dx = dead_rows_buffer((N, H), x.device) if (ctx.inner & 2) else torch.zeros((N, H), dtype=torch.float32, device=x.device)
-                dbn, db2n = node_chain_bwd(dxn, H1n, dXP[:, H:], ctx.chain_panels[1], ctx.residual, slope, nd.tiles, dPn, dS, dx)
-            elif nd is not None:
-                # dPn = act'(H1n) (.) (dxn W2) on the kept nodes' tiles; db2n = the column sums of the dxn rows it fetches
-                dPn, dbn, db2n = bwd_h1_typed(dxn, nW2, H1n, nd.tiles, slope, out=dXP[:, :H])
-                if vcodes:
-                    dW2n = atb_rows(dxn, H1n, ctx.v_gate, colsum=False)[0]
-            elif onepanel_ok(H) and atb_ok(dxn, H1n):
-                # as on the edge side: the node gate lives inside the two consumers of dO = v_gate * dxn
-                if binary_gate_mask(ctx.v_gate) is not None:
-                    # a 0 / 1 node gate: db2n from the rows bwd_h1 fetches, the weight gradient(s) ungated over the masked-in rows
-                    dPn, dbn, db2n = bwd_h1_mfma(dxn, nW2, H1n, both_halves=False, gate=ctx.v_gate, out=dXP[:, :H], slope=slope,
-                                                 rows_colsum=True)
-                    if not one_launch or vcodes:
-                        dW2n = atb_rows(dxn, H1n, ctx.v_gate, colsum=False)[0]
-                else:
-                    if not one_launch or vcodes:
-                        dW2n, db2n = atb_rows(dxn, H1n, ctx.v_gate)
-                    dPn, dbn = bwd_h1_mfma(dxn, nW2, H1n, both_halves=False, gate=ctx.v_gate, out=dXP[:, :H], slope=slope)
-            else:
-                dOn, db2n = scale_rows_colsum(dxn, ctx.v_gate)
-                dW2n = wg(dOn, H1n)
-                dH1n = dOn @ nW2
-                dPn, dbn = relu_bwd_colsum_(dH1n, H1n, out=dXP[:, :H], slope=slope)
-            if l0 is not None:
-                # S = [S0_in W0 | S0_out W0] was never built: X[h] = S0_h^T dPn per table (N rows, K columns) carries both
-                # dBn_h = W0^T X[h] and the segment sums' part of the embedding gradient, sum_h X[h] Bn_h^T (no dS either)
-                Kp, S0 = l0.enc.size(1), ctx.l0_S0
-                Xn = (torch.empty if full else torch.zeros)((2, TK, H), dtype=torch.float32, device=dPn.device)
-                xjobs = [(S0[n0:n1, h * Kp:h * Kp + K0], dPn[n0:n1], Xn[h, t * K0:(t + 1) * K0],
-                          nd.mask[n0 // 32:] if nd is not None else None) for t, _, (n0, n1) in tables if n1 > n0 for h in (0, 1)]
-                if 0 < len(xjobs) <= 4 and dPn.stride(1) == 1 and dPn.stride(0) % 2 == 0 and dPn.data_ptr() % 8 == 0:
-                    smallk_atb_jobs(xjobs, H)          # both tables x both halves: one launch
-                    xjobs = []
-                for t, _, (n0, n1) in (tables if xjobs else []):
-                    if n1 > n0:
-                        for h in (0, 1):
-                            if nd is not None:     # (dPn's rows of the dead nodes were not written: masked out)
-                                smallk_atb_cols(S0[n0:n1, h * Kp:h * Kp + K0], dPn[n0:n1], None, Xn[h, t * K0:(t + 1) * K0].unsqueeze(0), H,
-                                                mask=nd.mask[n0 // 32:])
-                            else:
-                                smallk_atb(S0[n0:n1, h * Kp:h * Kp + K0], dPn[n0:n1], out=Xn[h, t * K0:(t + 1) * K0])
-                dS = dBn = dWx = None
-                if vcodes:
-                    # x = venc WV0:  x^T dXP = WV0^T (venc^T dXP)  and  venc^T dx = venc^T dxn + (venc^T dXP) Wx^T -- N-row
-                    # passes on K columns instead of two [N,H] x [H,3H] products and the three-block weight gradient
-                    VK, TVK = l0.VK, WV0.size(0)
-                    vfull = all(n1 > n0 for _, (n0, n1) in l0.vtables(N)) and len(l0.vtables(N)) * VK == TVK
-                    Yn = (torch.empty if vfull else torch.zeros)((4 if ctx.residual else 3, TVK, H), dtype=torch.float32, device=dPn.device)
-                    vmask = getattr(l0, "venc_mask", None)
-                    for t, (n0, n1) in l0.vtables(N):
-                        # (the packed node codes carry the node gate: a gated-out node's code row is all zeros)
-                        # (one table over all nodes under the node gate: the kept nodes' list -- a node outside it has a zero code row)
-                        klist = nd.rows if (nd is not None and n0 == 0 and n1 == N) else None
-                        smallk_atb_cols(l0.venc[n0:n1, :VK], dXP[n0:n1], dxn[n0:n1] if ctx.residual else None,
-                                        Yn[:, t * VK:(t + 1) * VK], H,
-                                        mask=vmask[n0 // 32:] if (klist is None and vmask is not None and n0 % 32 == 0) else None, rows=klist)
-                elif one_launch:
-                    vm = binary_gate_mask(ctx.v_gate)
-                    if nd is not None:     # over the kept nodes' tiles
-                        (dW2n, _), (dWx, _) = atb_rows_multi([(dxn, H1n, None, False), (x, dXP, None, False)], tiles=nd.tiles)
-                    elif vm is not None:    # (db2n came from bwd_h1; no job carries a gate: the launch runs on the bf16 pipe)
-                        (dW2n, _), (dWx, _) = atb_rows_multi([(dxn, H1n, None, False, vm), (x, dXP, None, False)])
-                    else:
-                        (dW2n, db2n), (dWx, _) = atb_rows_multi([(dxn, H1n, ctx.v_gate, True, gate_row_mask(ctx.v_gate)), (x, dXP, None, False)])
-                else:
-                    dWx = wg(x, dXP)
-            else:
-                if chained:
-                    pass
-                elif nd is not None:     # dS = dPn Bn^T on the kept nodes' tiles; the edge kernel reads a dead node's rows as zeros
-                    dS = dead_rows_buffer((N, 2 * H), x.device)
-                    jobs = [dict(a=dPn, W=Bn[:H], w_in_out=False, out=dS[:, :H]), dict(a=dPn, W=Bn[H:], w_in_out=False, out=dS[:, H:])]
-                    if ctx.needs_input_grad[3]:    # ... and in the same launch two of the three partial products of dx = dxn + dXP Wx^T
-                        dxU = dead_rows_buffer((N, 2 * H), x.device)
-                        jobs += [dict(a=dXP[:, :H], W=Wx[:, :H], w_in_out=False, prev=dxn if ctx.residual else None, out=dxU[:, :H]),
-                                 dict(a=dXP[:, H:2 * H], W=Wx[:, H:2 * H], w_in_out=False, out=dxU[:, H:])]
-                    typed_jobs(jobs, nd.tiles)
-                else:
-                    dS = dPn @ Bn.t()
-                if one_launch:   # the three node-side weight gradients (1 + 2 + 3 output blocks) share one launch
-                    # (dPn = act'(H1n) ((v_gate dxn) W2): zero rows under a zero node gate -- the first two products skip them)
-                    vm = gate_row_mask(ctx.v_gate)
-                    if nd is not None:
-                        # the three products over the kept nodes' tiles (rows gathered by slot): 41 % of the row tiles at
-                        # bench.py's labels, and nothing of a dead node's (unwritten) rows is touched
-                        (dW2n, _), (dBn, _), (dWx, _) = atb_rows_multi([(dxn, H1n, None, False), (S, dPn, None, False), (x, dXP, None, False)],
-                                                                        tiles=nd.tiles)
-                    elif binary_gate_mask(ctx.v_gate) is not None:   # (db2n came from bwd_h1; no job carries a gate: bf16 pipe)
-                        (dW2n, _), (dBn, _), (dWx, _) = atb_rows_multi([(dxn, H1n, None, False, vm), (S, dPn, None, False, vm),
-                                                                         (x, dXP, None, False)])
-                    else:
-                        (dW2n, db2n), (dBn, _), (dWx, _) = atb_rows_multi([(dxn, H1n, ctx.v_gate, True, vm), (S, dPn, None, False, vm),
-                                                                            (x, dXP, None, False)])
-                else:
-                    dBn = wg(S, dPn)                                         # [2H,H]
-                    dWx = wg(x, dXP)                                         # [H,3H] = [dA_n | dPd | dPs]
-            if chained:
-                pass
-            elif ctx.needs_input_grad[3] and nd is not None:
-                # dx = dxn + dXP Wx^T on the kept nodes' tiles: the third 128-deep block of the contraction + the two partial
-                # products made beside dS.  A dead node's row is multiplied by the gate's zero further down: left unwritten
-                # where the layer before is the only reader (``inner`` bit 1), zeros for whoever made the first layer's rows
-                dx = dead_rows_buffer((N, H), x.device) if (ctx.inner & 2) else torch.zeros((N, H), dtype=torch.float32, device=x.device)
-                if l0 is None:
-                    out_fwd_typed(dXP[:, 2 * H:], Wx[:, 2 * H:], None, dxU[:, :H], nd.tiles, out=dx, w_in_out=False, prev2=dxU[:, H:])
-                else:      # (a first layer on the label codes of its edge rows only: no dS launch to share)
-                    for b3 in range(3):
-                        out_fwd_typed(dXP[:, b3 * H:(b3 + 1) * H], Wx[:, b3 * H:(b3 + 1) * H], None,
-                                      (dxn if ctx.residual else None) if b3 == 0 else dx, nd.tiles, out=dx, w_in_out=False)
-            elif ctx.needs_input_grad[3]:
-                dx = torch.addmm(dxn, dXP, Wx.t()) if ctx.residual else dXP @ Wx.t()
-            # ---- edge side, input gradient: residual + seg_sum2 backward + GEMM, accumulated in place
-            dz = None
-            if l0 is None and ctx.needs_input_grad[4]:
-                # the input gradient of an edge under a zero of a gate that wiped the rep-net's input rows is multiplied by that
-                # zero further down: not computed.  After the first layer (``inner`` bit 1) its reader is the layer before,
-                # which leaves those rows out; the first layer hands zeros to whoever made the rows.
-                dead_dz = (("leave" if (ctx.inner & 2) else "zero") if dead_edge_rows(ix, H, ctx.e_gate) else None)
-                dst_m = None if nd is None else nd.sel[2]      # (dS's rows of the dead nodes were not written: read as zeros)
-                both = None
-                if typed and dWes is None:
-                    base_ = (lazy[0] if lazy is not None else dzn) if ctx.residual else None
-                    both = bwd_z_w(dG, z, Wes, dS, base_, coef, ix, ctx.WesT, base_map=lazy[1] if (lazy is not None and ctx.residual) else None,
-                                   gate=ctx.e_gate, dead_rows=dead_dz, dst=dst_m)
-                    if both is None:
-                        dWes = atb_typed(z, dG, coef, ix, gate=ctx.e_gate)
-                if both is not None:
-                    dz, dWes = both
-                elif lazy is not None:
-                    dz = bwd_z_typed(dG, dG.stride(0), Wes, dS, lazy[0] if ctx.residual else None, coef, ix, ctx.WesT,
-                                     base_map=lazy[1] if ctx.residual else None, gate=ctx.e_gate, dead_rows=dead_dz, dst=dst_m)
-                elif typed:
-                    dz = bwd_z_typed(dG, dG.stride(0), Wes, dS, dzn if ctx.residual else None, coef, ix, ctx.WesT, gate=ctx.e_gate,
-                                     dead_rows=dead_dz, dst=dst_m)
-                elif mfma:
-                    dz = bwd_z_mfma(dG, Wes, dS, dzn if ctx.residual else None, coef, ix)
-                else:
-                    dz = ops.gather_select_raw(dS, ix.dst32, ix.rev8, H, None, -1.0, 1.0,
-                                               base=dzn if ctx.residual else None)
-                    dz.addmm_(dG, Wes.t())
-        dW0 = dWV0 = None
-        if l0 is not None:       # after the reductions of the block above have run: ONE launch
-            # dWes = W0^T (enc^T [dPre | c dPre]);  dBn_h = W0^T X_h;  enc^T dz = (enc^T [dPre | c dPre]) [A | B]^T + sum_h X_h Bn_h^T
-            # (+ enc^T dzn);  dWx = WV0^T (venc^T dXP) block by block;  venc^T dx = sum_b Y_b Wx_b^T (+ venc^T dxn)
-            dev = XX.device
-            dWes = torch.empty((H, 2 * H), dtype=torch.float32, device=dev)
-            dBn = torch.empty((2 * H, H), dtype=torch.float32, device=dev)
-            dW0 = torch.empty((W0.size(0), H), dtype=torch.float32, device=dev)
-            jobs = [(dWes, [(W0, True, XX[:, :2 * H], False)], None),
-                    (dBn[:H], [(W0, True, Xn[0], False)], None), (dBn[H:], [(W0, True, Xn[1], False)], None),
-                    (dW0, [(XX[:, :2 * H], False, Wes, True), (Xn[0], False, Bn[:H], True), (Xn[1], False, Bn[H:], True)],
-                     XX[:, 2 * H:] if ctx.residual else None)]
-            if vcodes:
-                dWx = torch.empty((H, 3 * H), dtype=torch.float32, device=dev)
-                dWV0 = torch.empty((WV0.size(0), H), dtype=torch.float32, device=dev)
-                for b3 in range(3):
-                    jobs.append((dWx[:, b3 * H:(b3 + 1) * H], [(WV0, True, Yn[b3], False)], None))
-                jobs.append((dWV0, [(Yn[b3], False, Wx[:, b3 * H:(b3 + 1) * H], True) for b3 in range(3)], Yn[3] if ctx.residual else None))
-            small_gemm_jobs(jobs)
+                dWes = _edge_first_wgrad(c, z, dG, typed, want_dz)
+                dBn, dbn, dWx, dW2n, db2n, dS, dx = _node_bwd_rows(c, ctx.chain_panels, x, S, H1n, dxn, dXP, want_dx)
+                if want_dz:
+                    dz, dWes = _edge_input_grad(c, z, dG, dS, dzn, lazy, dWes, typed)
+        if c.l0 is not None:
+            dBn, dWx, dWes, dW0, dWV0 = _l0_final_products(c, XX, Xn, Yn, dWx)
         return (None, None, None, dx, dz, None, None, dBn, dbn, dWx, dWes, dbe, dW2n, db2n, dW2e, db2e, None, None, None, None,
                 None, None, None, dW0, dWV0, None, None)
 

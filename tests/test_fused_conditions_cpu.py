@@ -85,6 +85,21 @@ def test_the_dead_row_conditions_as_a_truth_table():
     assert len(seen) == 2 * 2 * 2 * 2             # two gate forms, H 64 / 128, tables at node 0 / 32, with and without node codes
 
 
+def test_the_two_panel_kernels_limits_lie_inside_the_class_typed_kernels():
+    """``mfma_ok(ix, H)`` implies ``typed_ok(ix, H)``: the fused layer asks ``typed_ok`` alone, no two-panel route stands behind its
+    failure (H = 128 is an admitted width, N * 3H * 4 < 2^32 gives N < 2^31, E * 4 < 2^32 is E < 2^30)."""
+    from dualmessagepassing_amd import fused
+    rows = (1 << 32) // 1536
+    both = []
+    for N, E, H in itertools.product((0, 4096, rows - 1, rows, rows + 1, (1 << 31) - 1, 1 << 31), (0, (1 << 30) - 1, 1 << 30),
+                                     (32, 64, 96, 128, 256)):
+        ix = types.SimpleNamespace(num_nodes=N, num_edges=E)
+        if fused.mfma_ok(ix, H):
+            assert fused.typed_ok(ix, H), (N, E, H)
+            both.append((N, E, H))
+    assert (4096, 0, 128) in both
+
+
 def test_a_first_layer_row_range_walks_a_list_from_an_aligned_start_and_a_minimum_of_rows():
     from dualmessagepassing_amd import fused
     m = fused.L0_LIST_MIN_ROWS
