@@ -262,6 +262,11 @@ SIGNATURES = {
     "dmp_csr_build_pair": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                    c_ptr, c_ptr]),
     "dmp_heads_blend": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr]),
+    "dmp_pool_out": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
+                             c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "dmp_rows_gemm": (c_int, [c_ptr, c_i64, c_i64, c_int, c_ptr, c_int, c_ptr, c_i64, c_ptr]),
+    "dmp_pool_wgrad_blocks": (c_i64, [c_i64]),
+    "dmp_pool_wgrad": (c_int, [c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
     "dmp_concat_pairs": (c_int, [_p(dmp_concat_job), c_int, c_ptr]),
     "dmp_table_rows": (c_int, [_p(dmp_lookup_job), c_int, c_ptr]),
     "dmp_len_masks": (c_int, [_p(dmp_mask_job), c_int, c_i64, c_ptr]),

@@ -382,6 +382,205 @@ __global__ __launch_bounds__(kLossThreads) void count_loss_k(const float *__rest
   if (threadIdx.x == 0) loss[0] = red[0] * inv_n;
 }
 
+// ------------------------------------------------------------------ the pooled last layer's per-graph algebra
+// The turn-around of a step whose last layer hands out per-graph sums only (fused._pooled_outputs, _edge_out_bwd_lazy): the
+// second level of the pooled sums (chunk -> graph), the [G, h] x [h, h] products with the second Linear's weight and the two
+// parameter gradients, on arrays of a few thousand rows -- three launches on the tiles above instead of nine dependent ones
+// (segment sums, library products, a row pass) of 5 .. 16 us each.  fp32 throughout.
+constexpr int kWgGraphs = 32;     // graphs per workgroup of pool_wgrad_k: its rows in LDS -> one [h, h + 1] partial
+
+// A thread's CW columns (from `col`) of one graph's second-level sum: the rows `gent[p] >> 1` of the chunk table, p =
+// gptr[g] .. gptr[g + 1] - 1, added one by one from zero in that order -- the order and the bits of seg_sum_vec over the same
+// CSR.  Four rows are requested together.  (An entry outside the table's V rows is left out, never read.)  `part2` (may be
+// NULL; block-uniform): a second table of the same shape over the same CSR into `acc2`, its rows requested with the first's.
+template <int CW>
+__device__ __forceinline__ void chunk_sum(float (&acc)[CW], float (&acc2)[CW], const float *part, const float *part2, int64_t ld,
+                                          int64_t V, const int32_t *gptr, const int32_t *gent, int64_t g, int col) {
+  constexpr int U = 4;
+#pragma unroll
+  for (int e = 0; e < CW; ++e) { acc[e] = 0.f; acc2[e] = 0.f; }
+  const int beg = gptr[g], end = gptr[g + 1];
+  for (int p = beg; p < end; p += U) {
+    float4 v[U][CW / 4], v2[U][CW / 4];
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      ok[u] = false;
+      if (p + u < end) {
+        const int64_t ch = gent[p + u] >> 1;
+        ok[u] = ch >= 0 && ch < V;
+        if (ok[u]) {
+#pragma unroll
+          for (int q = 0; q < CW / 4; ++q) v[u][q] = ldg4(part + ch * ld + col + 4 * q);
+          if (part2) {
+#pragma unroll
+            for (int q = 0; q < CW / 4; ++q) v2[u][q] = ldg4(part2 + ch * ld + col + 4 * q);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (ok[u]) {
+#pragma unroll
+        for (int q = 0; q < CW / 4; ++q) {
+          acc[4 * q] += v[u][q].x; acc[4 * q + 1] += v[u][q].y; acc[4 * q + 2] += v[u][q].z; acc[4 * q + 3] += v[u][q].w;
+        }
+        if (part2) {
+#pragma unroll
+          for (int q = 0; q < CW / 4; ++q) {
+            acc2[4 * q] += v2[u][q].x; acc2[4 * q + 1] += v2[u][q].y; acc2[4 * q + 2] += v2[u][q].z; acc2[4 * q + 3] += v2[u][q].w;
+          }
+        }
+      }
+    }
+  }
+}
+
+struct PoolOut {
+  const float *partH, *partZ, *partX, *gcnt, *W2, *b2;
+  const int32_t *gptr, *gent, *ngptr, *ngent;
+  float *es, *vs, *Q;
+  int64_t ldh, V, Vn;
+  int G, Gn, halves, eblocks;
+};
+
+// Forward.  Workgroups 0 .. eblocks - 1, 16 graphs each: Q = the non-flagged half of the chunk sums of g (.) H1, summed per
+// graph;  es = sum of z's chunk sums + Q W2^T + gcnt[:, 0] b2.  The workgroups after them: vs = the node chunk sums per graph.
+template <int kH>
+__global__ __launch_bounds__(kThreads) void pool_out_k(const PoolOut a) {
+  constexpr int kPad = HeadGeom<kH>::kPad, CW = HeadGeom<kH>::CW;
+  __shared__ float As[kRows * kPad];
+  __shared__ float Ws[16 * kPad];
+  const int tid = threadIdx.x, r = tid >> 4, cg = tid & 15, col = cg * CW;
+  float q[CW], zs[CW];
+  if ((int)blockIdx.x >= a.eblocks) {
+    const int64_t g = (int64_t)((int)blockIdx.x - a.eblocks) * kRows + r;
+    if (g >= a.Gn) return;
+    chunk_sum<CW>(q, zs, a.partX, nullptr, kH, a.Vn, a.ngptr, a.ngent, g, col);
+    store_cw<CW>(a.vs + g * kH + col, q);
+    return;
+  }
+  const int64_t g = (int64_t)blockIdx.x * kRows + r;
+  const bool live = g < a.G;
+#pragma unroll
+  for (int e = 0; e < CW; ++e) { q[e] = 0.f; zs[e] = 0.f; }
+  // (both tables' rows in one walk of the CSR: the residual term's loads do not wait behind the product)
+  if (live) chunk_sum<CW>(q, zs, a.partH, a.partZ, a.ldh, a.V, a.gptr, a.gent, g, col);
+  const float cnt = (live && a.b2) ? a.gcnt[g * a.halves] : 0.f;
+  store_cw<CW>(&As[r * kPad + col], q);
+  if (live && a.Q) store_cw<CW>(a.Q + g * kH + col, q);
+  float es[CW];
+#pragma unroll
+  for (int e = 0; e < CW; ++e) es[e] = 0.f;
+  gemm_h<kH>(es, As, kPad, a.W2, kH, 1, 0, Ws, tid, cg);
+  if (!live) return;
+  if (a.partZ) {
+#pragma unroll
+    for (int e = 0; e < CW; ++e) es[e] = zs[e] + es[e];
+  }
+  if (a.b2) {
+#pragma unroll
+    for (int e = 0; e < CW; ++e) es[e] += cnt * a.b2[col + e];
+  }
+  store_cw<CW>(a.es + g * kH + col, es);
+}
+
+// out = A op(W): a plain [rows, h] x [h, h] product, 16 rows per workgroup (wT as gemm_h's).
+template <int kH>
+__global__ __launch_bounds__(kThreads) void rows_gemm_k(const float *__restrict__ A, int64_t lda, int rows, const float *__restrict__ W, int wT,
+                                                        float *__restrict__ out, int64_t ldo) {
+  constexpr int kPad = HeadGeom<kH>::kPad, CW = HeadGeom<kH>::CW;
+  __shared__ float As[kRows * kPad];
+  __shared__ float Ws[16 * kPad];
+  const int tid = threadIdx.x, r = tid >> 4, cg = tid & 15, i0 = (int)blockIdx.x * kRows;
+  float acc[CW];
+#pragma unroll
+  for (int e = 0; e < CW; ++e) acc[e] = 0.f;
+  stage_rows<kH>(As, A, lda, i0, rows, tid);
+  gemm_h<kH>(acc, As, kPad, W, kH, wT, 0, Ws, tid, cg);
+  if (i0 + r < rows) store_cw<CW>(out + (int64_t)(i0 + r) * ldo + cg * CW, acc);
+}
+
+struct PoolWgrad {
+  const float *qc, *T, *gcnt;
+  const int32_t *gptr, *gent;
+  float *part, *Q;
+  int64_t ldq, ldt, V;
+  int G, halves;
+};
+
+// Backward, after pool_relu_bwd.  A workgroup owns kWgGraphs graphs: their Q rows (the non-flagged half of the chunk sums qc,
+// per graph; thread (r, cg) sums h / 8 columns of row r) and T rows go to LDS, then  dW2 = T^T Q  (MFMA: A = T^T, the
+// contraction runs over the graphs; wave w owns the output rows (h/4) w ..) and  db2 = sum_g gcnt[g, 0] T[g], graphs ascending.
+// Its partial [h * h | h] is one row of `part`: no atomics, dmp_reduce_partials adds the workgroups' rows.
+template <int kH>
+__global__ __launch_bounds__(kThreads) void pool_wgrad_k(const PoolWgrad a) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  constexpr int CW = kH / 8, JT = kH / 64, KT = kH / 16;
+  constexpr int kWPad = kH + 16;      // the MFMA operands are read down a column: the four rows of a k step in disjoint banks
+  __shared__ float Ts[kWgGraphs * kWPad];
+  __shared__ float Qs[kWgGraphs * kWPad];
+  __shared__ float Cs[kWgGraphs];
+  const int tid = threadIdx.x, r = tid >> 3, cg = tid & 7, col = cg * CW;
+  const int lane = tid & 63, wave = tid >> 6, m = lane & 15, kq = lane >> 4;
+  const int64_t g = (int64_t)blockIdx.x * kWgGraphs + r;
+  const bool live = g < a.G;
+  float q[CW], tv[CW], unused[CW];
+#pragma unroll
+  for (int e = 0; e < CW; ++e) { q[e] = 0.f; tv[e] = 0.f; }
+  if (live) {
+#pragma unroll
+    for (int v = 0; v < CW / 4; ++v) {
+      const float4 t4 = ldg4(a.T + g * a.ldt + col + 4 * v);
+      tv[4 * v] = t4.x; tv[4 * v + 1] = t4.y; tv[4 * v + 2] = t4.z; tv[4 * v + 3] = t4.w;
+    }
+    if (cg == 0) Cs[r] = a.gcnt[g * a.halves];
+    chunk_sum<CW>(q, unused, a.qc, nullptr, a.ldq, a.V, a.gptr, a.gent, g, col);
+    if (a.Q) store_cw<CW>(a.Q + g * kH + col, q);
+  } else if (cg == 0) {
+    Cs[r] = 0.f;
+  }
+  store_cw<CW>(&Qs[r * kWPad + col], q);
+  store_cw<CW>(&Ts[r * kWPad + col], tv);
+  __syncthreads();
+  f32x4 d[JT][KT];
+#pragma unroll
+  for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) d[jt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < kWgGraphs / 4; ++s) {
+    const int row = (4 * s + kq) * kWPad;
+    float av[JT];
+#pragma unroll
+    for (int jt = 0; jt < JT; ++jt) av[jt] = Ts[row + (wave * JT + jt) * 16 + m];
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+      const float b = Qs[row + kt * 16 + m];
+#pragma unroll
+      for (int jt = 0; jt < JT; ++jt) d[jt][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[jt], b, d[jt][kt], 0, 0, 0);
+    }
+  }
+  float *P = a.part + (int64_t)blockIdx.x * (kH * kH + kH);
+#pragma unroll
+  for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) P[((wave * JT + jt) * 16 + 4 * kq + i) * kH + kt * 16 + m] = d[jt][kt][i];
+  if (tid < kH) {
+    float db = 0.f;
+#pragma unroll
+    for (int rr = 0; rr < kWgGraphs; ++rr) db += Cs[rr] * Ts[rr * kWPad + tid];
+    P[kH * kH + tid] = db;
+  }
+}
+
+inline bool pool_csr_ok(const int32_t *gptr, const int32_t *gent, int64_t V, int64_t G) {
+  return gptr && (gent || V == 0) && V >= 0 && G >= 0 && G < ((int64_t)1 << 24) && V < ((int64_t)1 << 30);
+}
+
 }  // namespace
 }  // namespace dmp
 
@@ -455,6 +654,56 @@ int dmp_count_loss(const float *pred, const float *target, int64_t n, int kind, 
   if (n < 1 || kind < 0 || kind > 2 || !pred || !target || !loss || !dpred) return DMP_ERR_BAD_ARG;
   if (n > ((int64_t)1 << 22) || !(neg_slope >= 0.f && neg_slope <= 1.f)) return DMP_ERR_UNSUPPORTED;     // (one workgroup: a batch's counts)
   count_loss_k<<<1, kLossThreads, 0, (hipStream_t)stream>>>(pred, target, n, kind, neg_slope, loss, dpred);
+  return check_launch();
+}
+
+int dmp_pool_out(const float *partH, const float *partZ, int64_t V, int halves, const int32_t *gptr, const int32_t *gent, int64_t G,
+                 const float *gcnt, const float *W2, const float *b2, const float *partX, int64_t Vn, const int32_t *ngptr,
+                 const int32_t *ngent, int64_t Gn, int H, float *es, float *vs, float *Q, void *stream) {
+  if (H != 128 && H != 64) return DMP_ERR_UNSUPPORTED;
+  if ((halves != 1 && halves != 2) || !pool_csr_ok(gptr, gent, V, G)) return DMP_ERR_BAD_ARG;
+  if (G > 0 && (((V > 0 || partH) && !ok16p(partH)) || (partZ && !ok16p(partZ)) || !ok16p(W2) || (b2 && (!ok16p(b2) || !gcnt)) || !ok16p(es) || (Q && !ok16p(Q))))
+    return DMP_ERR_BAD_ARG;
+  if (!partX) Gn = 0;
+  if (partX && (!pool_csr_ok(ngptr, ngent, Vn, Gn) || (Gn > 0 && (!ok16p(partX) || !ok16p(vs))))) return DMP_ERR_BAD_ARG;
+  if (G == 0 && Gn == 0) return DMP_OK;
+  PoolOut a;
+  a.partH = partH; a.partZ = partZ; a.partX = partX; a.gcnt = gcnt; a.W2 = W2; a.b2 = b2;
+  a.gptr = gptr; a.gent = gent; a.ngptr = ngptr; a.ngent = ngent; a.es = es; a.vs = vs; a.Q = Q;
+  a.ldh = (int64_t)halves * H; a.V = V; a.Vn = Vn; a.G = (int)G; a.Gn = (int)Gn; a.halves = halves;
+  a.eblocks = (int)((G + kRows - 1) / kRows);
+  const unsigned grid = (unsigned)(a.eblocks + (Gn + kRows - 1) / kRows);
+  if (H == 128) pool_out_k<128><<<grid, kThreads, 0, (hipStream_t)stream>>>(a);
+  else pool_out_k<64><<<grid, kThreads, 0, (hipStream_t)stream>>>(a);
+  return check_launch();
+}
+
+int dmp_rows_gemm(const float *A, int64_t lda, int64_t rows, int H, const float *W, int w_out_in, float *out, int64_t ldo,
+                  void *stream) {
+  if (H != 128 && H != 64) return DMP_ERR_UNSUPPORTED;
+  if (rows < 0 || rows >= ((int64_t)1 << 30) || lda < H || ldo < H || lda % 4 || ldo % 4) return DMP_ERR_BAD_ARG;
+  if (rows == 0) return DMP_OK;
+  if (!ok16p(A) || !ok16p(W) || !ok16p(out)) return DMP_ERR_BAD_ARG;
+  const unsigned grid = (unsigned)((rows + kRows - 1) / kRows);
+  if (H == 128) rows_gemm_k<128><<<grid, kThreads, 0, (hipStream_t)stream>>>(A, lda, (int)rows, W, w_out_in ? 1 : 0, out, ldo);
+  else rows_gemm_k<64><<<grid, kThreads, 0, (hipStream_t)stream>>>(A, lda, (int)rows, W, w_out_in ? 1 : 0, out, ldo);
+  return check_launch();
+}
+
+int64_t dmp_pool_wgrad_blocks(int64_t G) { return G > 0 ? (G + kWgGraphs - 1) / kWgGraphs : 0; }
+
+int dmp_pool_wgrad(const float *qc, int64_t ldq, int64_t V, int halves, const int32_t *gptr, const int32_t *gent, int64_t G,
+                   const float *T, int64_t ldt, const float *gcnt, int H, float *partial, float *Q, void *stream) {
+  if (H != 128 && H != 64) return DMP_ERR_UNSUPPORTED;
+  if ((halves != 1 && halves != 2) || !pool_csr_ok(gptr, gent, V, G) || ldt < H || ldt % 4 || ldq < H || ldq % 4) return DMP_ERR_BAD_ARG;
+  if (G == 0) return DMP_OK;
+  if (((V > 0 || qc) && !ok16p(qc)) || !ok16p(T) || !gcnt || !ok16p(partial) || (Q && !ok16p(Q))) return DMP_ERR_BAD_ARG;
+  PoolWgrad a;
+  a.qc = qc; a.T = T; a.gcnt = gcnt; a.gptr = gptr; a.gent = gent; a.part = partial; a.Q = Q;
+  a.ldq = ldq; a.ldt = ldt; a.V = V; a.G = (int)G; a.halves = halves;
+  const unsigned grid = (unsigned)dmp_pool_wgrad_blocks(G);
+  if (H == 128) pool_wgrad_k<128><<<grid, kThreads, 0, (hipStream_t)stream>>>(a);
+  else pool_wgrad_k<64><<<grid, kThreads, 0, (hipStream_t)stream>>>(a);
   return check_launch();
 }
 

@@ -157,11 +157,12 @@ def relu_bwd_gathered_colsum(table, rowmap, gate, act, slope=0.0):
     return out, reduce_partials(part)
 
 
-def pool_relu_bwd(table, rowmap, gate, act, pool, slope=0.0, skip_dead=False):
+def pool_relu_bwd(table, rowmap, gate, act, pool, slope=0.0, skip_dead=False, chunk_sums=False):
     """``relu_bwd_gathered_colsum`` and ``pool_rows(act, pool, gate)`` in ONE pass over ``act`` (``dmp_pool_relu_bwd``):
     -> (dPre [R, H], column sums of dPre [H], Q [graphs, 2H] = gated per-graph sums of ``act`` by flag).
     ``skip_dead`` (every consumer of dPre leaves out the rows under a zero of the 0 / 1 ``gate``): the pass walks the kept
-    rows' chunk table (``keep_pool_csr``) -- dPre's rows under a zero gate are not stored, nor are their entries walked."""
+    rows' chunk table (``keep_pool_csr``) -- dPre's rows under a zero gate are not stored, nor are their entries walked.
+    ``chunk_sums``: the third result is the pass's own [chunks, 2H] table instead of Q (``pool_wgrad`` sums it per graph itself)."""
     lib = _lib.load()
     R, H = act.shape
     V = pool.num_chunks
@@ -174,6 +175,8 @@ def pool_relu_bwd(table, rowmap, gate, act, pool, slope=0.0, skip_dead=False):
     with _lib.timed("pool_relu_bwd[H=%d,R=%d]", (H, R), 8 * H * R + 12 * R + 8 * H * V):
         check(lib.dmp_pool_relu_bwd(ptr(act), act.stride(0), ptr(table), table.stride(0), ptr(rowmap), ptr(gate), ptr(vptr),
                                     ptr(vent), V, R, H, slope, ptr(out), H, ptr(qc), ptr(part), stream_ptr()), "dmp_pool_relu_bwd")
+    if chunk_sums:
+        return out, reduce_partials(part), qc
     Q = ops.seg_sum_raw(qc, pool.gptr, pool.gent, pool.num_graphs, None, False, rows_shared=False)
     return out, reduce_partials(part), Q
 
@@ -208,13 +211,86 @@ def pool_rows(x, pool, weight=None):
     """Per-graph sums of the rows of ``x`` over ``pool`` (``ops.PoolIndex``): [G, H], or [G, 2H] = [non-flagged | flagged] when
     the index carries a flag; ``weight`` [rows]: a row scale (a 0 / 1 gate: the pass runs over the kept rows' chunk table,
     ``keep_pool_csr``).  Raw (no autograd): two launches of the segment-sum kernel."""
+    return ops.seg_sum_raw(pool_chunk_sums(x, pool, weight), pool.gptr, pool.gent, pool.num_graphs, None, False, rows_shared=False)
+
+
+def pool_chunk_sums(x, pool, weight=None):
+    """The first level of ``pool_rows``: the sums of the rows of ``x`` per chunk of ``pool`` -> [chunks, H] (with a flag [chunks, 2H])."""
     split = pool.flag8 is not None
     kc = keep_pool_csr(pool, weight) if (weight is not None and x.size(1) % 4 == 0 and x.is_contiguous()) else None
     if kc is not None:
-        part = ops.seg_sum_raw(x, kc[0], kc[1], pool.num_chunks, None, split, 1.0, 1.0, rows_shared=False)
-    else:
-        part = ops.seg_sum_raw(x, pool.vptr, pool.vent, pool.num_chunks, weight, split, 1.0, 1.0, rows_shared=False)
-    return ops.seg_sum_raw(part, pool.gptr, pool.gent, pool.num_graphs, None, False, rows_shared=False)
+        return ops.seg_sum_raw(x, kc[0], kc[1], pool.num_chunks, None, split, 1.0, 1.0, rows_shared=False)
+    return ops.seg_sum_raw(x, pool.vptr, pool.vent, pool.num_chunks, weight, split, 1.0, 1.0, rows_shared=False)
+
+
+USE_POOL_ALGEBRA = True     # the pooled last layer's per-graph algebra as three launches (``pool_out``, ``rows_gemm``, ``pool_wgrad``)
+POOL_ALGEBRA_WIDTHS = (64, 128)
+
+
+def _aligned(*tensors):
+    """Contiguous fp32 tensors at 16-byte aligned addresses (None passes)."""
+    return all(t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0) for t in tensors)
+
+
+def pool_algebra_ok(index, H, epool, eW2, eb2):
+    """The ONE host condition of the three-launch route, for both passes of a call of the layer's row-less form (kept on its
+    ``_LayerCall``): the kernels' widths, fp32 parameters they can read as float4, an index over rows in their own order (the
+    gated counts, ``pool_weight_sums``), and the conditions of the backward's lazy form (``_grad_seeds``), whose algebra this is."""
+    return bool(USE_POOL_ALGEBRA and H in POOL_ALGEBRA_WIDTHS and getattr(epool, "rows_in_order", False) and epool.num_graphs > 0
+                and index.num_edges > 0 and typed_ok(index, H) and eb2 is not None and _aligned(eW2, eb2))
+
+
+def pool_out(partH, partZ, pool, gcnt, W2, b2, partX=None, vpool=None, want_q=False):
+    """The second level of the pooled sums and the second Linear on them in ONE launch (``dmp_pool_out``):
+    ``es [G, H] = sum_chunks partZ[:, :H] + (sum_chunks partH[:, :H]) W2^T + gcnt[:, 0] b2`` over the chunk sums of ``pool``
+    (``pool_chunk_sums``: the non-flagged half only), ``vs [Gn, H] = sum_chunks partX`` over ``vpool``'s; chunks in ascending
+    order: ``vs`` and the inner ``Q`` have ``pool_rows``' bits -> ``(es, vs or None[, Q])``."""
+    lib = _lib.load()
+    H, G, V = W2.size(0), pool.num_graphs, pool.num_chunks
+    halves = partH.size(1) // H
+    dev = partH.device
+    es = torch.empty((G, H), dtype=torch.float32, device=dev)
+    Q = torch.empty((G, H), dtype=torch.float32, device=dev) if want_q else None
+    Gn, Vn = (vpool.num_graphs, vpool.num_chunks) if partX is not None else (0, 0)
+    vs = torch.empty((Gn, H), dtype=torch.float32, device=dev) if partX is not None else None
+    nbytes = 4 * H * (V * (2 if partZ is not None else 1) + H + G + Vn + Gn) + 4 * (V + Vn + 2 * G + Gn)
+    with _lib.timed("pool_out[H=%d,G=%d]", (H, G), nbytes):
+        check(lib.dmp_pool_out(ptr(partH), ptr(partZ), V, halves, ptr(pool.gptr), ptr(pool.gent), G, ptr(gcnt), ptr(W2), ptr(b2),
+                               ptr(partX), Vn, ptr(vpool.gptr) if partX is not None else None,
+                               ptr(vpool.gent) if partX is not None else None, Gn, H, ptr(es), ptr(vs), ptr(Q), stream_ptr()),
+              "dmp_pool_out")
+    return (es, vs, Q) if want_q else (es, vs)
+
+
+def rows_gemm(a, W, w_out_in):
+    """``a W^T`` (``w_out_in``: ``W`` in nn.Linear layout) or ``a W`` for [rows, H] x [H, H] on the heads' tiles (``dmp_rows_gemm``)."""
+    lib = _lib.load()
+    R, H = a.shape
+    out = torch.empty((R, H), dtype=torch.float32, device=a.device)
+    with _lib.timed("rows_gemm[H=%d,R=%d]", (H, R), 4 * H * (2 * R + H)):
+        check(lib.dmp_rows_gemm(ptr(a), a.stride(0) if R > 1 else H, R, H, ptr(W), int(bool(w_out_in)), ptr(out), H, stream_ptr()),
+              "dmp_rows_gemm")
+    return out
+
+
+def pool_wgrad(qc, pool, T, gcnt, want_q=False):
+    """The second Linear's parameter gradients from the per-graph table ``T`` alone (``dmp_pool_wgrad``): with ``Q`` = the per-graph
+    sums of the non-flagged half of the chunk sums ``qc`` (formed in LDS, chunks ascending), ``dW2 = T^T Q`` and ``db2 = gcnt[:, 0] T``
+    as per-workgroup partials, finished by ``reduce_partials`` (deferred inside ``deferred_reductions``) -> ``(dW2, db2[, Q])``."""
+    lib = _lib.load()
+    G, H = T.shape
+    V = pool.num_chunks
+    nb = int(lib.dmp_pool_wgrad_blocks(G))
+    if nb == 0:
+        z = torch.zeros(H * H + H, dtype=torch.float32, device=T.device)
+        return (z[:H * H].view(H, H), z[H * H:]) + ((torch.empty((0, H), dtype=torch.float32, device=T.device),) if want_q else ())
+    part = torch.empty((nb, H * H + H), dtype=torch.float32, device=T.device)
+    Q = torch.empty((G, H), dtype=torch.float32, device=T.device) if want_q else None
+    with _lib.timed("pool_wgrad[H=%d,G=%d]", (H, G), 4 * H * (V + G) + 4 * (V + 2 * G) + 4 * nb * (H * H + H)):
+        check(lib.dmp_pool_wgrad(ptr(qc), qc.size(1), V, gcnt.size(1), ptr(pool.gptr), ptr(pool.gent), G, ptr(T), T.stride(0) if G > 1 else H, ptr(gcnt),
+                                 H, ptr(part), ptr(Q), stream_ptr()), "dmp_pool_wgrad")
+    out = reduce_partials(part)
+    return (out[:H * H].view(H, H), out[H * H:]) + ((Q,) if want_q else ())
 
 
 def pool_weight_sums(pool, weight=None):
@@ -1810,7 +1886,7 @@ class _LayerCall:
     """The immutable facts of one call of the fused layer, built once in ``_FusedDMPLayer.forward`` and kept on ``ctx``: what the
     stages of both passes read and none of them writes.  What a stage MAKES travels through its arguments and its return value."""
     __slots__ = ("index", "coef", "residual", "H", "N", "slope", "inner", "v_gate", "e_gate", "Bn", "bn", "Wx", "Wes", "be",
-                 "nW2", "nb2", "eW2", "eb2", "WesT", "nW2t", "eW2t", "l0", "W0", "WV0", "nd", "vpool", "epool")
+                 "nW2", "nb2", "eW2", "eb2", "WesT", "nW2t", "eW2t", "l0", "W0", "WV0", "nd", "vpool", "epool", "poolalg")
 
     def __init__(self, **facts):
         for name in self.__slots__:
@@ -2075,6 +2151,18 @@ def _pooled_outputs(c, z, xn, zn, H1e, sums_only):
     """Stage (the LAST layer under pooling heads): the per-graph sums of both outputs -> ``(vs, es, gcnt)``; ``gcnt``: the gated
     row counts per graph of the row-less form (``sums_only``: no ``zn``), which the backward's db2 needs again."""
     H, epool, e_gate, eW2, eb2 = c.H, c.epool, c.e_gate, c.eW2, c.eb2
+    if c.poolalg:       # (``pool_algebra_ok``: the row-less form; the chunk tables the launch reads are this stage's own)
+        # the three first-level passes, then ONE launch: their second level, the product with W2 on the non-flagged half
+        # (the only one handed out), the bias and the residual term (csrc/dmp_heads.hip)
+        vp = c.vpool if (c.vpool is not None and c.vpool.flag8 is None) else None
+        partX = pool_chunk_sums(xn, vp) if vp is not None else None
+        partH = pool_chunk_sums(H1e, epool, e_gate)
+        gcnt = pool_weight_sums(epool, e_gate)
+        partZ = pool_chunk_sums(z, epool, e_gate if zero_rows_gate(e_gate) else None) if c.residual else None
+        es, vs = pool_out(partH, partZ, epool, gcnt, eW2, eb2, partX, vp)
+        if vp is None and c.vpool is not None:
+            vs = pool_rows(xn, c.vpool)
+        return vs, es, gcnt
     vs = pool_rows(xn, c.vpool) if c.vpool is not None else None
     if not sums_only:
         return vs, (pool_rows(zn, epool) if epool is not None else None), None
@@ -2157,6 +2245,16 @@ def _edge_out_bwd_lazy(c, H1e, lazy, gcnt):
     """The edge side's second Linear backward from the per-graph table alone (``_grad_seeds``) -> ``(dG, dbe, dW2e, db2e)``."""
     H, e_gate = c.H, c.e_gate
     T, emap, ep = lazy
+    if c.poolalg:
+        # three launches on the per-graph tiles (csrc/dmp_heads.hip): T W2, the one pass over H1e, then both parameter
+        # gradients from the pass's chunk sums -- their second level is formed inside, their partials join the layer's reduction
+        T = T if _aligned(T) else T.clone(memory_format=torch.contiguous_format)
+        skip = c.l0 is None and c.nd is not None and USE_PLAIN_ATB and dead_edge_rows(c.index, H, e_gate, c.coef)
+        dG, dbe, qc = pool_relu_bwd(rows_gemm(T, c.eW2, False), emap, e_gate, H1e, ep, c.slope, skip_dead=skip, chunk_sums=True)
+        if gcnt is None:
+            gcnt = pool_weight_sums(ep, e_gate)
+        dW2e, db2e = pool_wgrad(qc, ep, T, gcnt)
+        return dG, dbe, dW2e, db2e
     if H % 4 == 0 and H <= 256:
         # (dPre's rows under a zero of a 0 / 1 gate: every reader below leaves them out -- the kept incidence sums,
         # the class-tile kernels over the kept edges' tiles)
@@ -2534,11 +2632,13 @@ class _FusedDMPLayer(torch.autograd.Function):
         _lib.require_gpu(x, z)
         H = Bn.size(1)
         x, z = x.contiguous(), z.contiguous()
+        sums_only = epool is not None and not edge_rows
         c = _LayerCall(index=index, coef=coef, residual=residual, H=H, N=index.num_nodes, slope=slope, inner=int(inner),
                        v_gate=v_gate, e_gate=e_gate, Bn=Bn.contiguous(), bn=bn, Wx=Wx.contiguous(), Wes=Wes.contiguous(), be=be,
                        nW2=nW2, nb2=nb2, eW2=eW2, eb2=eb2, WesT=WesT, nW2t=nW2t, eW2t=eW2t, l0=l0,
                        W0=None if l0 is None else W0.detach(), WV0=None if (l0 is None or WV0 is None) else WV0.detach(),
-                       nd=_kept_nodes(index, H, v_gate, l0), vpool=vpool, epool=epool)
+                       nd=_kept_nodes(index, H, v_gate, l0), vpool=vpool, epool=epool,
+                       poolalg=sums_only and pool_algebra_ok(index, H, epool, eW2, eb2))
         # ---- node side (dmpnn.py:113,121,125 + fn.sum + 129-140)
         S = S0 = M0 = tables = xn = chain_panels = None
         if l0 is not None:
@@ -2548,7 +2648,6 @@ class _FusedDMPLayer(torch.autograd.Function):
         if xn is None:
             xn = _node_out(c, x, H1n)
         # ---- edge side (dmpnn.py:112,120,124 + 142-156)
-        sums_only = epool is not None and not edge_rows
         if l0 is not None:
             H1e, zn = _edge_first_codes(c, z, M0, tables, P, ldp, sums_only)
         else:

@@ -1052,6 +1052,34 @@ int dmp_match_loss(const float *pred, int64_t ldp, const int64_t *w, const uint8
 int dmp_heads_blend(const float *const *y, const float *const *gl, float *const *w, int num_heads, int B, float *out,
                     void *stream);
 
+/*
+ * The per-graph algebra of a pooled LAST layer that hands out sums only (the turn-around of a step: a few thousand rows),
+ * on the heads' 16-row fp32 MFMA tiles.  H = 128 or 64, else DMP_ERR_UNSUPPORTED; fp32 throughout.  (gptr [G + 1], gent):
+ * the chunk-to-graph CSR of a pooling index (entry >> 1 = a row of the chunk table, of V rows); a chunk table's row is
+ * [halves * H] = [non-flagged | flagged], halves = 1 or 2, of which only the non-flagged half is read.  Chunks are added one
+ * by one in CSR order from zero: the bits of dmp_seg_sum over the same CSR; a graph without chunks sums to zero.  Every float
+ * array 16-byte aligned; a NULL or misaligned one: DMP_ERR_BAD_ARG.  Q [G, H] (may be NULL): the per-graph sums of partH / qc
+ * as the kernel formed them.
+ *
+ * dmp_pool_out (forward):   es [G, H] = sum_chunks partZ[:, :H] + (sum_chunks partH[:, :H]) W2^T + gcnt[:, 0] b2
+ *                           vs [Gn, H] = sum_chunks partX          (the node index's CSR; partX [Vn, H])
+ *   partZ NULL: no residual term; b2 NULL: no bias term; partX NULL: no node sums (vs is not touched).  gcnt [G, halves];
+ *   W2 [H, H] in nn.Linear layout.
+ * dmp_rows_gemm:            out [rows, ldo >= H] = A W^T (w_out_in = 1: W [out, in], nn.Linear layout) or A W (0); A [rows, lda >= H].
+ * dmp_pool_wgrad (backward): with Q = sum_chunks qc[:, :H] per graph, a workgroup's slice of graphs gives one row of
+ *   partial [dmp_pool_wgrad_blocks(G), H * H + H] = [T^T Q | sum_g gcnt[g, 0] T[g]];  T [G, ldt >= H].  dmp_reduce_partials over
+ *   the rows finishes dW2 and db2: no atomics, a fixed order.  qc [V, ldq >= H] (its first H columns are read),
+ *   gcnt [G, halves].
+ */
+int dmp_pool_out(const float *partH, const float *partZ, int64_t V, int halves, const int32_t *gptr, const int32_t *gent, int64_t G,
+                 const float *gcnt, const float *W2, const float *b2, const float *partX, int64_t Vn, const int32_t *ngptr,
+                 const int32_t *ngent, int64_t Gn, int H, float *es, float *vs, float *Q, void *stream);
+int dmp_rows_gemm(const float *A, int64_t lda, int64_t rows, int H, const float *W, int w_out_in, float *out, int64_t ldo,
+                  void *stream);
+int64_t dmp_pool_wgrad_blocks(int64_t G);
+int dmp_pool_wgrad(const float *qc, int64_t ldq, int64_t V, int halves, const int32_t *gptr, const int32_t *gent, int64_t G,
+                   const float *T, int64_t ldt, const float *gcnt, int H, float *partial, float *Q, void *stream);
+
 
 /* ------------------------------------------------------------------------- */
 /* Fused MFMA kernels of the edge chain (fp32 MFMA, exact fp32).  H = 128; the one-panel kernels (dmp_out_fwd_fused_rows,
