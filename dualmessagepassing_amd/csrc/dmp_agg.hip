@@ -814,9 +814,15 @@ int dmp_compgcn_agg(const float *X, int64_t ldx, const float *Z, int64_t ldz, co
                     int comp, float *out, int64_t ldo, void *stream) {
   if (N < 0 || H <= 0 || ldx < H || ldz < H || ldo < 2 * H || comp < 0 || comp > 2) return DMP_ERR_BAD_ARG;
   if (N == 0) return DMP_OK;
-  if (!X || !Z || !rowptr || !ent || !src || !out) return DMP_ERR_BAD_ARG;
+  if (!rowptr || !out) return DMP_ERR_BAD_ARG;
   if (N >= kMaxRows) return DMP_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
+  if (!Z || !ent || !src) {  // a graph without edges (as seg_sum_impl): every sum is empty, whatever the composition
+    hipError_t e = hipMemset2DAsync(out, sizeof(float) * (size_t)ldo, 0, sizeof(float) * 2 * (size_t)H, (size_t)N, st);
+    if (e != hipSuccess) { set_last_hip_error(e); return DMP_ERR_HIP; }
+    return DMP_OK;
+  }
+  if (!X) return DMP_ERR_BAD_ARG;
   if (vec_ok(H, {ldx, ldz, ldo}, {X, Z, out})) {
     DMP_DISPATCH_G(H, {
       const unsigned nb = blocks_for(N, kBlock / G);

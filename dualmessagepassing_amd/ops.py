@@ -452,6 +452,8 @@ class _CompGCNAgg(torch.autograd.Function):
         Z, ldz = _mat(Z)
         dS, ldd = _mat(dS)
         E, H = ix.num_edges, X.size(1)
+        if E == 0:      # a graph without edges: the forward wrote zeros that depend on nothing
+            return X.new_zeros((X.size(0), H)), X.new_empty((0, H)), None, None, None
         dZ = torch.empty((E, H), dtype=torch.float32, device=X.device)
         dXe = torch.empty((E, H), dtype=torch.float32, device=X.device)
         check(lib.dmp_compgcn_agg_bwd(ptr(dS), ldd, ptr(X), ldx, ptr(Z), ldz, ptr(ix.src32), ptr(ix.dst32),

@@ -535,7 +535,8 @@ int dmp_edge_combine_bwd_g(const float *dY, int64_t ldy, const float *coef,
  *           domain: the DFT is linear, so the transform of the rows is a product with a fixed matrix on either side of the
  *           sum (X D, Z D before; D^-1 [W_in; W_out] folded into the N-row product after) and no per-edge FFT exists
  *     out[v, 0:H ] = sum_{e->v, flag=0} m_e ;  out[v, H:2H] = sum_{e->v, flag=1} m_e
- * so that node_agg = out @ [W_in ; W_out].  norm may be NULL.
+ * so that node_agg = out @ [W_in ; W_out].  norm may be NULL.  A graph without edges (Z, ent or src NULL, num_nodes > 0):
+ * the 2H columns of every row of out are set to zero, as dmp_seg_sum does.
  */
 int dmp_compgcn_agg(const float *X, int64_t ldx, const float *Z, int64_t ldz,
                     const int32_t *rowptr, const int32_t *ent,
