@@ -247,6 +247,12 @@ SIGNATURES = {
     "dmp_l0_node_pack_rows": (c_i64, []),
     "dmp_l0_node_fwd": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr, c_f32, c_ptr,
                                 c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+    "dmp_l0_node_fwd_mfma_max_codes": (c_int, []),
+    "dmp_l0_node_fwd_mfma": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_f32, c_ptr,
+                                     c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+    "dmp_l0_node_codes_bwd_blocks": (c_i64, [c_i64]),
+    "dmp_l0_node_codes_bwd": (c_int, [c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_int, c_int, c_int, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr,
+                                      c_ptr, c_i64, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
     "dmp_bn_partial_rows": (c_i64, [c_i64, c_int]),
     "dmp_bn_train_fwd": (c_int, [c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_f32, c_f32, c_ptr, c_ptr, c_int, c_f32, c_ptr, c_ptr, c_ptr,
                                  c_i64, c_ptr]),

@@ -1509,6 +1509,89 @@ def l0_node_fwd(venc, VK, S0, K0, Kp, W, bias, slope, mask, n0, n1, H, h1, P, ro
                                   ptr(h1), h1.stride(0), ptr(P), P.stride(0), stream_ptr()), "dmp_l0_node_fwd")
 
 
+USE_L0_NODE_MFMA = True        # the first layer's node side from the label codes as ONE launch on the matrix pipe (csrc/dmp_l0node.hip)
+L0_NODE_MFMA_MAX_CODES = 16    # ... whose k-groups hold that many columns of venc / S0_in / S0_out each (dmp_l0_node_fwd_mfma_max_codes)
+
+
+def l0_node_mfma_ok(H, VK, K0, Kp, tables, N, venc, S0, exact_fp32=None):
+    """Whether ``l0_node_fwd_mfma`` takes the node side of a first layer (else ``l0_node_fwd`` per table): H = 128 on the bf16x6
+    products, node codes, at most ``L0_NODE_MFMA_MAX_CODES`` columns per block and ``L0_NODE_MAX_COLS`` together, at most two
+    tables, code rows of whole 16 bytes that the kernel's descriptors address (strides below 16 KiB, arrays below 4 GiB).
+    ``exact_fp32``: the development switch's state (None: asked of the library)."""
+    if not USE_L0_NODE_MFMA or H != 128 or venc is None or S0 is None or tables < 1 or tables > 2:
+        return False
+    if VK < 1 or K0 < 1 or VK > L0_NODE_MFMA_MAX_CODES or K0 > L0_NODE_MFMA_MAX_CODES or VK + 2 * K0 > L0_NODE_MAX_COLS:
+        return False
+    if exact_fp32 is None:
+        exact_fp32 = _lib.load().dmp_dev_get_exact_fp32()
+    if exact_fp32:
+        return False
+    lim = (1 << 32) - 65536
+    ldv, lds = venc.stride(0), S0.stride(0)
+    if Kp % 4 or Kp < K0 or lds < 2 * Kp or ldv < VK or ldv % 4 or lds % 4 or venc.data_ptr() % 16 or S0.data_ptr() % 16:
+        return False
+    return bool(ldv * 4 <= 16383 and lds * 4 <= 16383 and N * ldv * 4 < lim and N * lds * 4 < lim and N * 2 * H * 4 < lim)
+
+
+def l0_node_fwd_mfma(venc, VK, S0, K0, Kp, WP, row_split, bias, slope, N, H, h1, P, mask=None, rows=None, prefix=0):
+    """``l0_node_fwd`` for every embedding table in ONE launch on the matrix pipe (``dmp_l0_node_fwd_mfma``): ``WP`` [tables, ..,
+    3H] the packed matrices (``l0_node_pack``), a row below ``row_split`` taking the first; ``rows`` = ``NodeRows.rows`` (the kept
+    nodes over all N, whose first ``prefix`` entries are 0 .. prefix-1; None: every row), ``mask``: the nodes whose ``P`` rows are
+    written as zeros where their bit is 0.  A node outside ``rows`` is not read and its ``h1`` row stays unwritten."""
+    lib = _lib.load()
+    WP = WP if WP.dim() == 3 else WP.unsqueeze(0)
+    lst, cnt = rows if rows is not None else (None, None)
+    K = VK + 2 * K0
+    # (the host knows the kept rows only as far as the prefix: under a mask the count is what the launch moves at least -- every
+    # node's P row, zeros or not, and the prefix's code and H1n rows)
+    known = N if lst is None else min(int(prefix), N)
+    nbytes = 4 * (H + K) * known + (8 * H * N if (mask is not None or lst is None) else 8 * H * known) + (N // 8 if mask is not None else 0)
+    with _lib.timed("l0_node_mfma[K=%d,N=%d,kept>=%d]", (K, N, known), nbytes):
+        check(lib.dmp_l0_node_fwd_mfma(ptr(venc), venc.stride(0), VK, ptr(S0), S0.stride(0), K0, Kp, ptr(WP), WP.stride(1), WP.stride(0),
+                                       WP.size(0), int(row_split), ptr(bias), float(slope), ptr(mask), ptr(lst), ptr(cnt),
+                                       0 if lst is None else lst.numel(), 0 if lst is None else min(int(prefix), N, lst.numel()), N, H,
+                                       ptr(h1), h1.stride(0), ptr(P), P.stride(0), stream_ptr()), "dmp_l0_node_fwd_mfma")
+
+
+def l0_node_bwd_ok(H, VK, K0, Kp, tables, vtables, N, venc, S0, dXP, dxn=None, exact_fp32=None):
+    """Whether ``l0_node_codes_bwd`` takes the K-column products of a first layer's node side backward (else ``smallk_atb_jobs`` and
+    ``smallk_atb_cols``): the forward's condition, one venc table or one per table of S0, and gradient rows of whole 8 bytes
+    that the descriptors address."""
+    if not l0_node_mfma_ok(H, VK, K0, Kp, tables, N, venc, S0, exact_fp32) or vtables < 1 or vtables > tables or dXP is None:
+        return False
+    lim = (1 << 32) - 65536
+    for d, cols in ((dXP, 3 * H), (dxn, H)):
+        if d is None:
+            continue
+        ld = d.stride(0)
+        if d.stride(1) != 1 or d.size(1) < cols or ld % 2 or d.data_ptr() % 8 or ld * 4 > 16383 or N * ld * 4 >= lim:
+            return False
+    return True
+
+
+def l0_node_codes_bwd(venc, VK, vtables, S0, K0, Kp, tables, row_split, dXP, dxn, N, H, Xn, Yn, rows=None, prefix=0):
+    """``Xn[h, t K0 : (t+1) K0] = S0_h^T dXP[:, :H]`` per table and ``Yn[b, tv VK : (tv+1) VK] = venc^T (block b of [dXP | dxn])``
+    over the kept rows in ONE launch on the matrix pipe (``dmp_l0_node_codes_bwd``); the workgroups' partials join the deferred
+    reduction (``reduce_partials``): a fixed order, no atomics.  ``rows`` / ``prefix`` as for ``l0_node_fwd_mfma``."""
+    lib = _lib.load()
+    lst, cnt = rows if rows is not None else (None, None)
+    bound = N if lst is None else min(lst.numel(), N)
+    G = int(lib.dmp_l0_node_codes_bwd_blocks(bound))
+    nblk = 3 if dxn is None else 4
+    partX = torch.empty((G, 2 * tables * K0 * H), dtype=torch.float32, device=dXP.device)
+    partY = torch.empty((G, nblk * vtables * VK * H), dtype=torch.float32, device=dXP.device)
+    known = N if lst is None else min(int(prefix), N)
+    with _lib.timed("l0_node_bwd[K=%d,N=%d,kept>=%d]", (VK + 2 * K0, N, known),
+                    4 * (nblk * H + VK + 2 * K0) * known + 4 * (partX.numel() + partY.numel())):
+        check(lib.dmp_l0_node_codes_bwd(ptr(venc), venc.stride(0), VK, vtables, ptr(S0), S0.stride(0), K0, Kp, tables, int(row_split),
+                                        ptr(dXP), dXP.stride(0), ptr(dxn), 0 if dxn is None else dxn.stride(0), ptr(lst), ptr(cnt),
+                                        0 if lst is None else lst.numel(), 0 if lst is None else min(int(prefix), N, lst.numel()), N, H,
+                                        ptr(partX), ptr(partY), stream_ptr()), "dmp_l0_node_codes_bwd")
+    reduce_partials(partX, Xn.view(-1))
+    reduce_partials(partY, Yn.view(-1))
+    return Xn, Yn
+
+
 def l0_edge_fwd(enc, K, M, P, ldp, bias, coef, index, slope=0.0, rows=None, out=None, mask=None, mlp=None):
     """``act(enc M[:, :H] + coef[dst] enc M[:, H:] + P[a, 0:H] - P[b, H:2H] + bias)`` -- ``edge_fwd_typed`` for input rows
     ``enc W`` of rank K with ``M = W Wes``: no class tiles, rows in their own order.  ``rows = (r0, r1)``: only that range
@@ -1958,6 +2041,14 @@ def _node_first_codes(c, x, z):
         # (the kept nodes' H1n rows only; a dead node's projection rows are zeros)
         H1n = dead_rows_buffer((N, H), z.device) if nd is not None else torch.empty((N, H), dtype=torch.float32, device=z.device)
         PX = torch.empty((N, 2 * H), dtype=torch.float32, device=z.device)      # the gathered projections [P_dst | P_src]
+        # (a node gate WITHOUT the kept-node path -- DMP_ROW_MASKS=0, fewer than 4,096 nodes -- keeps the launch per table: there the
+        # step's gradients moved by 1e-4 of their largest entry under a last-bit change of P's kept rows, docs/HISTORY.md (ss))
+        if (nd is not None or c.v_gate is None) and l0_node_mfma_ok(H, l0.VK, K0, Kp, WP.size(0), N, l0.venc, S0):
+            # ... every table's rows in one launch on the matrix pipe (the kept nodes' tiles; a row below the split: the first table)
+            l0_node_fwd_mfma(l0.venc, l0.VK, S0, K0, Kp, WP, l0.nsplit if WP.size(0) == 2 else N, c.bn, c.slope, N, H, H1n, PX,
+                             mask=None if nd is None else nd.mask, rows=None if nd is None else nd.rows,
+                             prefix=0 if nd is None else nd.prefix)
+            return S0, M0, tables, H1n, PX, 2 * H
         for t, _, (n0, n1) in tables:
             if n1 > n0 and (nd is None or n1 <= nd.prefix):      # (no gate, or the pattern's nodes -- all kept: every row)
                 l0_node_fwd(l0.venc, l0.VK, S0, K0, Kp, WP[t], c.bn, c.slope, None, n0, n1, H, H1n, PX)
@@ -2550,8 +2641,20 @@ def _node_bwd_codes(c, tables, S0, x, H1n, dxn, dXP, want_dx):
     vcodes = c.l0.venc is not None
     one_launch, kernel = _node_one_launch(c, x, None, H1n, dxn, dXP), atb_ok(x, dXP)
     dPn, dbn, db2n, dW2n = _node_out_bwd(c, dxn, H1n, dXP, not one_launch or vcodes, kernel)
-    Xn = _l0_node_sum_products(c, tables, S0, dPn)
     Yn = dWx = None
+    l0, N, H = c.l0, c.N, c.H
+    stables, vtables = c.W0.size(0) // l0.K, (c.WV0.size(0) // l0.VK if vcodes else 0)
+    dres = dxn if c.residual else None
+    if vcodes and (c.nd is not None or c.v_gate is None) and l0_node_bwd_ok(H, l0.VK, l0.K, l0.enc.size(1), stables, vtables, N, l0.venc, S0,
+                                                                             dXP, dres):
+        # both families of K-column products from ONE pass over the kept nodes' gradient rows on the matrix pipe
+        Xn = torch.empty((2, c.W0.size(0), H), dtype=torch.float32, device=dXP.device)
+        Yn = torch.empty((4 if c.residual else 3, c.WV0.size(0), H), dtype=torch.float32, device=dXP.device)
+        nd = c.nd
+        l0_node_codes_bwd(l0.venc, l0.VK, vtables, S0, l0.K, l0.enc.size(1), stables, l0.nsplit if stables == 2 else N, dXP, dres, N, H,
+                          Xn, Yn, rows=None if nd is None else nd.rows, prefix=0 if nd is None else nd.prefix)
+        return dbn, dWx, dW2n, db2n, Xn, Yn, (_node_dx(c, dxn, dXP, None) if want_dx else None)
+    Xn = _l0_node_sum_products(c, tables, S0, dPn)
     if vcodes:
         Yn = _l0_node_code_products(c, dXP, dxn)
     elif one_launch:

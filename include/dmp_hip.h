@@ -720,6 +720,33 @@ int64_t dmp_l0_node_pack_rows(void);
 int dmp_l0_node_fwd(const float *venc, int64_t ldv, int VK, const float *S0, int64_t lds, int K0, int Kp, const float *W, int64_t ldw,
                     const float *bias, float slope, const uint32_t *rowmask, const int32_t *list, const int32_t *count, int64_t list_bound,
                     int64_t q_begin, int64_t n0, int64_t n1, int H, float *h1, int64_t ldh, float *P, int64_t ldp, void *stream);
+/* dmp_l0_node_fwd for EVERY embedding table as ONE launch on the matrix pipe (csrc/dmp_l0node.hip; H = 128, bf16x6): the kept node
+ * rows in 32-row tiles, a tile's code rows [venc | S0_in | S0_out] split into bf16 pieces once, against the packed matrices held as
+ * piece fragments.  W: `tables` (<= 2) packed matrices of VK + 2 K0 rows each (dmp_l0_node_fwd's packing), `wstride` floats apart; a
+ * row below row_split takes table 0, the others table 1 (tables == 1: table 0).  list / count (dmp_kept_rows over ALL N nodes,
+ * ascending; list_bound = the list's capacity; its first `prefix` entries are 0 .. prefix-1): the kept rows; NULL: the rows 0 .. N-1.
+ * rowmask (NULL: none): a node whose bit is 0 gets ZEROS in its P row; its h1 row is left unwritten, and nothing of it is read.
+ * VK, K0 <= dmp_l0_node_fwd_mfma_max_codes(), rows and strides of whole 16 bytes, arrays below 4 GiB; DMP_ERR_UNSUPPORTED otherwise
+ * and under the exact-fp32 switch (callers run dmp_l0_node_fwd per table). */
+int dmp_l0_node_fwd_mfma_max_codes(void);
+int dmp_l0_node_fwd_mfma(const float *venc, int64_t ldv, int VK, const float *S0, int64_t lds, int K0, int Kp, const float *W, int64_t ldw,
+                         int64_t wstride, int tables, int64_t row_split, const float *bias, float slope, const uint32_t *rowmask,
+                         const int32_t *list, const int32_t *count, int64_t list_bound, int64_t prefix, int64_t N, int H, float *h1,
+                         int64_t ldh, float *P, int64_t ldp, void *stream);
+/* The backward's contraction over the same rows as ONE launch (csrc/dmp_l0node.hip; H = 128, bf16x6 on the 16x16x32 MFMA): what
+ * dmp_smallk_atb_jobs (S0_h^T dPn) and dmp_smallk_atb_cols_* (venc^T [dXP | dxn]) make in two,
+ *     X[h][t K0 + c]  = sum over the rows r of table t of  S0[r, h Kp + c] dXP[r, 0:H]                    (h = 0, 1)
+ *     Y[b][tv VK + c] = sum over the rows r of venc table tv of  venc[r, c] (b < 3 ? dXP[r, b H : (b+1) H] : dxn[r, 0:H])
+ * over the kept rows (list / count / list_bound / prefix as for dmp_l0_node_fwd_mfma; NULL: the rows 0 .. N-1); a row below row_split
+ * belongs to table 0; vtables = 1: one venc table for every row, = stables: split like S0.  dxn NULL: three blocks.  The sums go out
+ * as PARTIALS of G = dmp_l0_node_codes_bwd_blocks(rows bound) workgroups -- partX [G][2][stables K0][H], partY [G][3 or 4][vtables VK][H]
+ * -- for dmp_reduce_partials: no atomics, a fixed order, a workgroup without rows writes zeros.  Nothing is read of a row outside the
+ * list.  DMP_ERR_UNSUPPORTED as for the forward (callers run the two launches). */
+int64_t dmp_l0_node_codes_bwd_blocks(int64_t rows_bound);
+int dmp_l0_node_codes_bwd(const float *venc, int64_t ldv, int VK, int vtables, const float *S0, int64_t lds, int K0, int Kp, int stables,
+                          int64_t row_split, const float *dXP, int64_t ldd, const float *dxn, int64_t ldx, const int32_t *list,
+                          const int32_t *count, int64_t list_bound, int64_t prefix, int64_t N, int H, float *partX, float *partY,
+                          void *stream);
 int64_t dmp_l0_bwd_w_blocks(int64_t rows);
 /* dmp_l0_bwd_w_masked with a row mask: bit r of rowmask[t] == 0 says the code row 32 t + r is all zeros (the row's gate was 0 when
  * dmp_l0_pack made it), so its dPre / dZn rows -- which would be multiplied by those zeros -- are not fetched. */
