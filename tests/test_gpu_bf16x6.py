@@ -11,6 +11,17 @@ The envelope asserted:
     cancellation (x and -x against equal weights), 2^100: the bf16x6 error is at most 3 x the exact-fp32 kernel's;
   * operands around 2^-118: the third piece (2^-16 below the value) falls under bf16's range, two pieces are left, the
     error is bounded by 2^-16 of the natural scale -- absolute errors below 1e-38; no value of a training run lives there.
+
+The kernels: the five above and the tile-list kernels of csrc/dmp_typed.hip and csrc/dmp_atb.hip that have an exact form as well --
+``out_fwd_typed``, ``bwd_h1_typed``, ``typed_jobs`` with two jobs, ``atb_typed(plain=True)`` as shipped (``atb_plain``) and with
+``USE_ATB2`` off, on csrc/dmp_atb.hip's own tile-list kernels (``atb_plain_tiles``; ``atb_tile_jobs``: the jobs form behind
+``atb_rows_multi(tiles=...)``) -- at H = 128 (4099 rows) and at H = 64 (1031 rows; the ``*_at_width_64`` tests, which keep the test ids of the
+H = 128 tests as they were), the last tile partial.  The kernels without an exact form: tests/test_gpu_bf16x6_only.py.
+
+The sparse ladder (bf16x6_cases.ladder, proved in tests/test_bf16x6_ladder_cpu.py): operands whose bf16 split is known exactly and
+in which each output element is ONE product of two such values, so that each of the six piece products is at least 4 x 2^-21 of
+the result.  Both forms of every kernel must be within 2^-21 of fp64 ELEMENT BY ELEMENT: a piece read from a wrong slot, or one
+piece product in another's place, cannot pass.
 """
 import pytest
 import torch as th
@@ -18,6 +29,9 @@ import torch as th
 pytestmark = pytest.mark.gpu
 
 FLOOR = 2.0 ** -24          # one fp32 rounding of the natural scale: below this both forms are "exact enough"
+FIVE = ["edge_fwd_typed", "bwd_z_typed", "atb_typed", "out_fwd", "bwd_h1"]
+KERNELS = FIVE + ["out_fwd_typed", "bwd_h1_typed", "atb_plain", "atb_plain_tiles", "atb_tile_jobs", "typed_jobs"]
+SCENARIOS = ["normal", "element_binades", "row_binades", "cancel", "small", "huge"]
 
 
 @pytest.fixture(scope="module")
@@ -26,22 +40,74 @@ def measured(gpu):
     return run_all(gpu)
 
 
-@pytest.mark.parametrize("scenario", ["normal", "element_binades", "row_binades", "cancel", "small", "huge"])
-@pytest.mark.parametrize("kernel", ["edge_fwd_typed", "bwd_z_typed", "atb_typed", "out_fwd", "bwd_h1"])
-def test_bf16x6_is_as_accurate_as_the_f32_mfma(kernel, scenario, measured):
+@pytest.fixture(scope="module")
+def measured64(gpu):
+    from bf16x6_cases import run_all
+    from dualmessagepassing_amd import fused
+
+    class _Sizes:
+        num_nodes, num_edges = 1, 1
+
+    assert fused.onepanel_ok(64) and fused.typed_ok(_Sizes, 64)
+    return run_all(gpu, h=64)
+
+
+def _as_accurate(kernel, scenario, measured):
     e6, e32, finite = measured[scenario][kernel]
+    print("%s on %s: bf16x6 %.3g  exact fp32 %.3g of the natural scale" % (kernel, scenario, e6, e32))
     assert finite
     assert e6 <= max(3.0 * e32, FLOOR), "%s on %s: bf16x6 %.3g vs exact fp32 %.3g of the natural scale" % (kernel, scenario, e6, e32)
     assert e6 <= 2e-6                                          # and in absolute terms: a few fp32 roundings of a 128-term sum
 
 
-@pytest.mark.parametrize("kernel", ["edge_fwd_typed", "bwd_z_typed", "atb_typed", "out_fwd", "bwd_h1"])
-def test_bf16x6_below_its_range_degrades_to_two_pieces(kernel, measured):
+def _two_pieces(kernel, measured):
     e6, e32, finite = measured["tiny"][kernel]
+    print("%s on tiny: bf16x6 %.3g  exact fp32 %.3g of the natural scale" % (kernel, e6, e32))
     assert finite and e32 <= 2e-6
     assert e6 <= 2.0 ** -16, "%s: %.3g" % (kernel, e6)
 
 
-def test_the_exact_switch_is_off_afterwards(measured):
+def _ladder(kernel, measured):
+    from bf16x6_cases import LADDER_BOUND
+    e6, e32, ok = measured["ladder"][kernel]
+    print("%s on the sparse ladder: bf16x6 %.3g  exact fp32 %.3g of the element (bound %.3g)" % (kernel, e6, e32, LADDER_BOUND))
+    assert ok, "%s: a result that is not finite, or not 0 where fp64 is 0" % kernel
+    assert e6 <= LADDER_BOUND, "%s: bf16x6 %.3g" % (kernel, e6)
+    assert e32 <= LADDER_BOUND, "%s: exact fp32 %.3g" % (kernel, e32)
+
+
+@pytest.mark.parametrize("scenario", SCENARIOS)
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_bf16x6_is_as_accurate_as_the_f32_mfma(kernel, scenario, measured):
+    _as_accurate(kernel, scenario, measured)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_bf16x6_below_its_range_degrades_to_two_pieces(kernel, measured):
+    _two_pieces(kernel, measured)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_every_piece_product_on_the_sparse_ladder(kernel, measured):
+    _ladder(kernel, measured)
+
+
+@pytest.mark.parametrize("scenario", SCENARIOS)
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_bf16x6_is_as_accurate_as_the_f32_mfma_at_width_64(kernel, scenario, measured64):
+    _as_accurate(kernel, scenario, measured64)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_bf16x6_below_its_range_degrades_to_two_pieces_at_width_64(kernel, measured64):
+    _two_pieces(kernel, measured64)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_every_piece_product_on_the_sparse_ladder_at_width_64(kernel, measured64):
+    _ladder(kernel, measured64)
+
+
+def test_the_exact_switch_is_off_afterwards(measured, measured64):
     from dualmessagepassing_amd import _lib
     assert not _lib.load().dmp_dev_get_exact_fp32()
