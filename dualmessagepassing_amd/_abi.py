@@ -33,6 +33,7 @@ DMP_LRP_MAX_NEIGHBOURS = 32                            # distinct out-neighbours
 DMP_LRP_MAX_SEQ_LEN = 6
 DMP_LRP_OVER_CAP, DMP_LRP_SELF_LOOP, DMP_LRP_DROPPED = 1, 2, 4      # bits of the status word of dmp_lrp_count / _fill
 DMP_RANK_BAD_TYPE = 1                                  # status word of dmp_rank_counts_typed: a type code above 62 was met
+DMP_RESIDENT_MAX_SLOTS = 4096                          # pairs (real + inert) of a batch dmp_collate_resident assembles
 
 
 # ---- the structs, named and ordered as in the header; pointers are c_void_p (assigned from ``data_ptr()`` / None)
@@ -146,6 +147,16 @@ class dmp_atb2_job(ctypes.Structure):
 class dmp_atb_job(ctypes.Structure):
     _fields_ = [("A", c_ptr), ("lda", c_i64), ("B", c_ptr), ("ldb", c_i64), ("gate", c_ptr), ("partial", c_ptr), ("partial_stride", c_i64),
                 ("ldp", c_int), ("partial_colsum", c_ptr), ("cs_ld", c_int), ("rowmask", c_ptr)]
+
+
+class dmp_resident_side(ctypes.Structure):
+    _fields_ = [("src", c_ptr), ("dst", c_ptr), ("vlabel", c_ptr), ("elabel", c_ptr), ("eid", c_ptr), ("rev", c_ptr), ("node_ptr", c_ptr),
+                ("edge_ptr", c_ptr)]
+
+
+class dmp_resident_batch(ctypes.Structure):
+    _fields_ = [("src", c_ptr), ("dst", c_ptr), ("num_nodes", c_ptr), ("num_edges", c_ptr), ("nid", c_ptr), ("vlabel", c_ptr), ("eid", c_ptr),
+                ("elabel", c_ptr), ("rev", c_ptr)]
 
 
 _p = ctypes.POINTER      # ``const dmp_X *``: takes an array ``(dmp_X * n)()``, ``byref(x)`` or None, nothing else
@@ -411,4 +422,6 @@ SIGNATURES = {
     "dmp_lrp_pool_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
     "dmp_lrp_pool_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_ptr,
                                  c_ptr, c_ptr, c_ptr, c_ptr]),
+    "dmp_collate_resident": (c_int, [_p(dmp_resident_side), c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, _p(dmp_resident_batch), c_ptr, c_ptr,
+                                     c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
 }

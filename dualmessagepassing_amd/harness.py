@@ -208,6 +208,12 @@ class PairDataset:
             views[int(seq_len)] = LRPPairs(self, seq_len)
         return views[int(seq_len)]
 
+    def resident(self, device):
+        """The view of this dataset that lives on ``device`` (``resident.ResidentPairs``): uploaded once, every batch then
+        assembled there by one launch from one small upload.  Same batches, bit for bit; opt-in."""
+        from .resident import ResidentPairs
+        return ResidentPairs(self, device)
+
     ARRAYS_PER_GRAPH = 9    # src, dst, num_nodes, num_edges, node id, node label, edge id, edge label, is_reversed
 
     def pad_buckets(self, batch_size, levels=4):
@@ -364,6 +370,9 @@ class LRPPairs(PairDataset):
     def subset(self, indices):
         return PairDataset.subset(self, indices).lrp(self.seq_len)
 
+    def resident(self, device):
+        raise NotImplementedError("LRPPairs.resident: the LRP view's batches carry permutation indexes the device store does not hold")
+
     def model_config(self, hid_dim=64, layers=3, rep_net="DMPLRP", **kw):
         kw.setdefault("lrp_seq_len", self.seq_len)
         return PairDataset.model_config(self, hid_dim, layers, rep_net, **kw)
@@ -434,6 +443,9 @@ class EdgeSeqPairs:
 
     def __len__(self):
         return len(self.samples)
+
+    def resident(self, device):
+        raise NotImplementedError("EdgeSeqPairs.resident: the edge-sequence view's batches are tuple sequences the device store does not hold")
 
     def batchify(self, indices, device, return_weights=None):
         from .edgeseq import EdgeSeq

@@ -1751,6 +1751,36 @@ int dmp_lrp_pool_bwd(const float *node_feat, const float *edge_feat, const float
                      const int32_t *entp, const float *dout, int64_t P, int64_t N, int64_t E, int in, int hid, int L, float *dnode,
                      float *dedge, float *dweight, int32_t *ws, void *stream);
 
+/* ---- A batch assembled on the device from a dataset that lives there (dmp_resident.hip; the arrays
+ * harness.PairDataset.batch_arrays builds on the host and uploads one by one, dataset.py:1604-1636 + train.py:606-607).
+ * The store, per side (pattern, graph): every sample's arrays back to back in narrow types, sample s at
+ * [node_ptr[s], node_ptr[s + 1]) / [edge_ptr[s], edge_ptr[s + 1]); per dataset counts [S] fp32, the samples' subisomorphism rows
+ * flattened back to back (subs, int32) and sub_ptr [S + 1].
+ * The plan [4 + slots + 5 (slots + 1)] int64, ONE array the host fills per batch:
+ *   plan[0 .. 4)   the node and the edge label of an inert pattern, then of an inert graph
+ *   sample [slots] the sample of a real slot (slots [0, real)), -1 for an inert slot ([real, slots))
+ *   then five exclusive prefix sums of [slots + 1] over the slots: pattern nodes, pattern edges, graph nodes, graph edges,
+ *   subisomorphism elements (a slot's size is the difference of its two entries; a real slot's sizes are its sample's).
+ * One launch writes every element of every output exactly once (no atomics, nothing read from the outputs):
+ *   real slot : src / dst / vlabel / eid / elabel / rev copied (widened to int64), counts copied, weight 1, its rows copied
+ *   inert slot: a ring  src = j % n, dst = (j % n + 1) % n, eid = j, rev = 0, both labels the plan's, counts 0, weight 0, no rows
+ *   both      : nid = 0 .. n - 1, num_nodes / num_edges [slots] from the plan; sample_ptr [slots + 1] = the fifth prefix sum;
+ *               sub_flat [sub_capacity]: the slots' rows back to back, zeros from sub_total (= the prefix sum's last entry) on.
+ * store and out are HOST arrays of two (pattern, graph).  weights may be NULL (no such output); a NULL sample_ptr means no tail
+ * (sub_flat NULL too); with a tail, sub_flat may be NULL only when sub_capacity is 0.  Every slot's node and edge count must be below 2^31 and an inert slot needs a node.  1 <= real <= slots <=
+ * DMP_RESIDENT_MAX_SLOTS, else DMP_ERR_UNSUPPORTED (callers assemble such a batch on the host). */
+typedef struct {
+  const int32_t *src, *dst, *vlabel, *elabel, *eid; const uint8_t *rev; const int64_t *node_ptr, *edge_ptr;
+} dmp_resident_side;
+typedef struct {
+  int64_t *src, *dst, *num_nodes, *num_edges, *nid, *vlabel, *eid, *elabel; uint8_t *rev;
+} dmp_resident_batch;
+#define DMP_RESIDENT_MAX_SLOTS 4096
+int dmp_collate_resident(const dmp_resident_side *store, const float *counts, const int32_t *subs, const int64_t *sub_ptr,
+                         const int64_t *plan, int64_t slots, int64_t real, const dmp_resident_batch *out, float *o_counts,
+                         float *o_weights, int64_t *sub_flat, int64_t sub_capacity, int64_t sub_total, int64_t *sample_ptr,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
