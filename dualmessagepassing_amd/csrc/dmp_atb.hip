@@ -395,18 +395,6 @@ __global__ __launch_bounds__(kGroupThreads, 2) void atb_jobs_k(const AtbJobs t) 
 constexpr int kAtbLdsBytes = 2 * 2 * kSub * kLdsStride * 4;   // 67584: above the 64 KB static limit -> dynamic LDS, opted in once
 constexpr int kAtbLdsBytes64 = 2 * 2 * kSub * 68 * 4;         // H = 64: 34816
 constexpr int atb_lds_bytes(int H) { return H == 128 ? kAtbLdsBytes : kAtbLdsBytes64; }
-// The dynamic-LDS opt-in is a per-device function attribute: set once per (kernel, device) -- a process that drives
-// several devices passes through here once for each (the writes of the flag race benignly: the call is idempotent).
-constexpr int kMaxDevices = 64;
-inline bool opt_in_lds(const void *kernel, int bytes, bool (&done)[kMaxDevices]) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-  if (done[dev]) return true;
-  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) { set_last_hip_error(e); return false; }
-  done[dev] = true;
-  return true;
-}
 template <int MODE, int H = 128>
 bool lds_ready() {
   static bool done[kMaxDevices] = {}, done_exact[kMaxDevices] = {}, done_big[kMaxDevices] = {};

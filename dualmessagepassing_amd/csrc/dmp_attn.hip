@@ -494,17 +494,9 @@ template <int DH> int64_t key_tiles(int64_t Lk) { return (Lk + Geo<DH>::KPW - 1)
 // the score cache goes above the 64 KiB default of dynamic LDS: opted in once per (kernel, device)
 constexpr int kCacheBytes = 4 * kRowsPerWave * kCacheLk * 4;
 template <int DH> constexpr int tile_bytes() { return 2 * Tile<DH>::FLOATS * 4; }
-constexpr int kMaxDevices = 64;
 template <int DH> bool cache_lds_ready() {
   static bool done[kMaxDevices] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-  if (done[dev]) return true;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&attn_fwd_kernel<DH, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kCacheBytes + tile_bytes<DH>());
-  if (e != hipSuccess) { set_last_hip_error(e); return false; }
-  done[dev] = true;
-  return true;
+  return opt_in_lds(reinterpret_cast<const void *>(&attn_fwd_kernel<DH, true>), kCacheBytes + tile_bytes<DH>(), done);
 }
 
 template <int DH>

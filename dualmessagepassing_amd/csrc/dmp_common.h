@@ -32,6 +32,26 @@ inline int check_launch() {
   return DMP_OK;
 }
 
+// The dynamic-LDS opt-in is a per-device function attribute: set once per (kernel, device) -- a process that drives
+// several devices passes through here once for each (the writes of the flag race benignly: the call is idempotent).
+// `done`: the kernel instantiation's own static record.
+constexpr int kMaxDevices = 64;
+inline bool opt_in_lds(const void *kernel, int bytes, bool (&done)[kMaxDevices]) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
+  if (done[dev]) return true;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) { set_last_hip_error(e); return false; }
+  done[dev] = true;
+  return true;
+}
+
+// the grid of a persistent kernel that walks a tile list: one workgroup per CU, no more than there are tiles
+inline unsigned one_per_cu_blocks(int64_t tiles_bound) {
+  const int64_t cap = 256;
+  return (unsigned)(tiles_bound < cap ? (tiles_bound > 0 ? tiles_bound : 1) : cap);
+}
+
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // The MLP activations of the layers: ReLU (slope 0) or LeakyReLU with negative slope a (the reference's default

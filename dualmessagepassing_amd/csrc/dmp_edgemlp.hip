@@ -19,7 +19,7 @@
 // only: H1 is bit-identical to dmp_edge_fwd_typed's and out to dmp_out_fwd_typed's on every kept row, whatever tile list the latter
 // walks.  One barrier per tile (LDS traffic only); tile k's image is written between barriers k and k+1 and read between k+1 and
 // k+2, so two buffers suffice; the per-row index arrays live in a ring of four (tile k+3's are written while tile k's are read).
-#include "dmp_mfma_common.h"
+#include "dmp_x6_tile.h"
 
 namespace dmp {
 namespace {
@@ -42,23 +42,18 @@ struct EdgeMlpArgs {
   float slope;
 };
 
-constexpr int kHE = 128, kThreadsE = 512;
-constexpr int kStrideD = (kHE + 8) / 2;             // dwords per image row: 128 bf16 + 8 of padding (68 = 4 mod 64: conflict-free ds_read_b128)
-constexpr int kPlaneD = kSub * kStrideD;            // one bf16 plane of a 32-row tile
-constexpr int kTileD = 3 * kPlaneD;                 // hi | mid | lo: 6528 dwords = 26112 bytes
-constexpr int kRing = 4;                            // tiles whose per-row indices are alive at once
-constexpr int kImgOffH = 2 * kTileD * 4;            // the H1 image behind the z image (two buffers each)
-constexpr int kScrOff = 4 * kTileD * 4;             // the eight waves' accumulator transposes
+// (the workgroup's geometry -- kMlpThreads, the image's kMlpStride / kMlpPlane / kMlpTile, kMlpRing -- is dmp_x6_tile.h's, shared with l0_edge_mlp_k)
+constexpr int kImgOffH = 2 * kMlpTile * 4;          // the H1 image behind the z image (two buffers each)
+constexpr int kScrOff = 4 * kMlpTile * 4;           // the eight waves' accumulator transposes
 constexpr int kRowsOff = kScrOff + 8 * 32 * kScrStride * 4;
-constexpr int kEdgeMlpLdsBytes = kRowsOff + 3 * kRing * kSub * 4;   // 104448 + 36864 + 1536 = 142848
-constexpr int kHalfE = kHE / 2, kGroupsE = kHalfE / 8;
+constexpr int kEdgeMlpLdsBytes = kRowsOff + 3 * kMlpRing * kSub * 4;   // 104448 + 36864 + 1536 = 142848
 
-__global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) {
+__global__ __launch_bounds__(kMlpThreads, 1) void edge_mlp_k(const EdgeMlpArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   uint32_t *const zimg = reinterpret_cast<uint32_t *>(lds);
   uint32_t *const himg = reinterpret_cast<uint32_t *>(lds + kImgOffH);
-  uint32_t *const rowA = reinterpret_cast<uint32_t *>(lds + kRowsOff);            // [kRing][32] each: row INDICES (-1: none)
-  uint32_t *const rowB = rowA + kRing * kSub, *const rowC = rowB + kRing * kSub;
+  uint32_t *const rowA = reinterpret_cast<uint32_t *>(lds + kRowsOff);            // [kMlpRing][32] each: row INDICES (-1: none)
+  uint32_t *const rowB = rowA + kMlpRing * kSub, *const rowC = rowB + kMlpRing * kSub;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const bool second = wave >= 4;
   const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5, cs = wave & 3;
@@ -67,7 +62,7 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
   float *const scr = reinterpret_cast<float *>(lds + kScrOff) + wave * (32 * kScrStride);
   const int lrow = lane >> 3, c4 = 32 * cs + (lane & 7) * 4;
   const uint32_t col4 = (uint32_t)c4 * 4u;
-  constexpr uint32_t kRowBytes = kHE * 4u;
+  constexpr uint32_t kRowBytes = kMlpH * 4u;
   constexpr uint32_t kNone = 0xFFFFFFFFu, kOOB = 0xFFFFF000u;
 
   // this workgroup's contiguous tile range (tiles are sorted by class)
@@ -78,46 +73,14 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
   const int mine = hi > lo ? hi - lo : 0;
   if (mine == 0) return;                                                          // (uniform per workgroup: before any barrier)
 
-  Split8 B6[kGroupsE];                    // the role's panel: fragment g = B[kHalfE h + 8 g .. + 7][col] as bf16 pieces
+  Split8 B6[kMlpGroups];                    // the role's panel: fragment g = B[kMlpHalf h + 8 g .. + 7][col] as bf16 pieces
   f32x16 acc;
-  // The tile's product on the bf16 pipe (typed_body's x6_tile).  Per 16-deep k-group g: six MFMAs on the three piece fragments of
-  // the image row li (this lane's 8 consecutive k = kHalfE h + 8 g ..: one ds_read_b128 per plane, requested one group ahead) and
-  // the panel fragment B6[g]; the caller's 16 actions are spread between them.
+  // The tile's product on the bf16 pipe (x6_kgroups, the "3 + 3" schedule): the A fragments are those of the image row li (this
+  // lane's 8 consecutive k = kMlpHalf h + 8 g ..), the caller's 16 actions are spread between the MFMAs.
   auto x6_tile = [&](const uint32_t *img, auto &&action) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const uint32_t *ar = img + li * kStrideD + (kHalfE / 2) * h;
-    Frag8 ah, am, al;
-    ah.v = *reinterpret_cast<const bf16x8 *>(ar);
-    am.v = *reinterpret_cast<const bf16x8 *>(ar + kPlaneD);
-    al.v = *reinterpret_cast<const bf16x8 *>(ar + 2 * kPlaneD);
-#pragma unroll
-    for (int g = 0; g < kGroupsE; ++g) {
-      Frag8 nh = ah, nm = am, nl = al;
-      if (g + 1 < kGroupsE) {
-        nh.v = *reinterpret_cast<const bf16x8 *>(ar + 4 * (g + 1));
-        nm.v = *reinterpret_cast<const bf16x8 *>(ar + kPlaneD + 4 * (g + 1));
-        nl.v = *reinterpret_cast<const bf16x8 *>(ar + 2 * kPlaneD + 4 * (g + 1));
-      }
-      const Split8 &bb = B6[g];
-      __builtin_amdgcn_sched_barrier(0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al.v, bb.hi.v, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.lo.v, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am.v, bb.mid.v, acc, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      action(2 * g);
-      __builtin_amdgcn_sched_barrier(0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am.v, bb.hi.v, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.mid.v, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.hi.v, acc, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      action(2 * g + 1);
-      ah = nh; am = nm; al = nl;
-    }
-  };
-  auto acc_to_scr = [&]() {                // the accumulator block through this wave's scratch: rows of 4 consecutive columns per lane
-#pragma unroll
-    for (int r = 0; r < 16; ++r) scr[((r & 3) + 8 * (r >> 2) + 4 * h) * kScrStride + li] = acc[r];
+    x6_kgroups<kMlpGroups>(PaddedRowRead<kMlpPlane>{img + li * kMlpStride + (kMlpHalf / 2) * h}, B6, acc, action);
   };
 
   if (!second) {
@@ -135,8 +98,8 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
     const uint32_t colA = (uint32_t)(gtid & 31) * 16u;
     const int srow = gtid >> 5;                               // this thread stages rows srow + 8 m, float4 piece gtid % 32
 
-    const rsrc_t rs_W = make_rsrc(p.W, (uint32_t)(kHE * p.ldw * 4));
-    const uint32_t w_first = (uint32_t)((int64_t)kHalfE * h * p.ldw + col) * 4u;
+    const rsrc_t rs_W = make_rsrc(p.W, (uint32_t)(kMlpH * p.ldw * 4));
+    const uint32_t w_first = (uint32_t)((int64_t)kMlpHalf * h * p.ldw + col) * 4u;
     const uint32_t w_step = __builtin_amdgcn_readfirstlane((int)(p.ldw * 4));     // bytes from k to k+1
     auto load_panel = [&](float c) {                          // W_g = A' + c B' (the sum and its split as in typed_body)
       // (the offsets hang off values the optimiser cannot see through: otherwise it hoists the address computations out of the
@@ -147,7 +110,7 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
       // 32 rows of both halves per round trip: while this role builds a panel the whole workgroup waits for it (the second role
       // stands at the barrier), so its dependent round trips are the launch's, not one of two workgroups'
 #pragma unroll
-      for (int s0 = 0; s0 < kHalfE; s0 += 32) {
+      for (int s0 = 0; s0 < kMlpHalf; s0 += 32) {
         float w0[32], w1[32];
 #pragma unroll
         for (int j = 0; j < 32; ++j) {
@@ -191,10 +154,10 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
       uint2 ph, pm, pl;
       split_pair(pre[m].x, pre[m].y, ph.x, pm.x, pl.x);
       split_pair(pre[m].z, pre[m].w, ph.y, pm.y, pl.y);
-      uint32_t *q = zimg + buf * kTileD + (srow + 8 * m) * kStrideD + (gtid & 31) * 2;
+      uint32_t *q = zimg + buf * kMlpTile + (srow + 8 * m) * kMlpStride + (gtid & 31) * 2;
       *reinterpret_cast<uint2 *>(q) = ph;
-      *reinterpret_cast<uint2 *>(q + kPlaneD) = pm;
-      *reinterpret_cast<uint2 *>(q + 2 * kPlaneD) = pl;
+      *reinterpret_cast<uint2 *>(q + kMlpPlane) = pm;
+      *reinterpret_cast<uint2 *>(q + 2 * kMlpPlane) = pl;
     };
     auto stage_scalars = [&](int par) {                       // per-row indices of the staged tile (threads < 32)
       if (gtid < kSub) {
@@ -213,8 +176,8 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
     // One tile: the MFMAs of tile k (z image k & 1) with, in their shadow, the staging of tile k+1 into the other buffer, the row
     // requests of tile k+2 and the id requests of tile k+3 (typed_body's order).
     auto tile_step = [&](int k, int par) {
-      const int buf = k & 1, nxt = (par + 1) & (kRing - 1);
-      x6_tile(zimg + buf * kTileD, [&](int i) {
+      const int buf = k & 1, nxt = (par + 1) & (kMlpRing - 1);
+      x6_tile(zimg + buf * kMlpTile, [&](int i) {
         if (i < 4) {}                                         // (the epilogue operands: requested by the previous tile's epilogue)
         else if (i < 8) stage_row(buf ^ 1, i - 4);
         else if (i == 8) stage_scalars(nxt);
@@ -224,9 +187,9 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
       });
     };
     auto epilogue = [&](int k, int par) {
-      uint32_t *const img = himg + (k & 1) * kTileD;
-      const int nxt = (par + 1) & (kRing - 1);
-      acc_to_scr();
+      uint32_t *const img = himg + (k & 1) * kMlpTile;
+      const int nxt = (par + 1) & (kMlpRing - 1);
+      acc_to_scr(scr, acc, h, li);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int rr = 8 * q + lrow;
@@ -242,10 +205,10 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
         uint2 ph, pm, pl;
         split_pair(pad ? 0.f : v.x, pad ? 0.f : v.y, ph.x, pm.x, pl.x);
         split_pair(pad ? 0.f : v.z, pad ? 0.f : v.w, ph.y, pm.y, pl.y);
-        uint32_t *w = img + rr * kStrideD + (c4 >> 1);
+        uint32_t *w = img + rr * kMlpStride + (c4 >> 1);
         *reinterpret_cast<uint2 *>(w) = ph;
-        *reinterpret_cast<uint2 *>(w + kPlaneD) = pm;
-        *reinterpret_cast<uint2 *>(w + 2 * kPlaneD) = pl;
+        *reinterpret_cast<uint2 *>(w + kMlpPlane) = pm;
+        *reinterpret_cast<uint2 *>(w + 2 * kMlpPlane) = pl;
         // this chunk's operand registers are free: request the NEXT tile's rows into them (its indices were staged during
         // this tile's MFMA phase, before the barrier); past the last tile they are out of range: zeros
         fetch_operand(nxt, q);
@@ -293,7 +256,7 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
         lds_barrier();           // (barrier k) tile k+1 is staged for everyone, everyone is done with tile k's z rows
         epilogue(k, par);
         ++k;
-        par = (par + 1) & (kRing - 1);
+        par = (par + 1) & (kMlpRing - 1);
       } while (k < mine && (k & 63) != 0 && ((starts >> (k & 63)) & 1ull) == 0);
     }
     lds_barrier();               // (barrier `mine`) the last tile's H1 image is complete
@@ -302,24 +265,13 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
     __builtin_amdgcn_s_setprio(1);                            // the later-dispatched half loses every arbitration otherwise
     float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (p.bias2) bias4 = *reinterpret_cast<const float4 *>(p.bias2 + c4);
-    const srsrc_t rs_R = make_srsrc(p.R, p.R ? p.ldr : (int64_t)kHE, p.E);        // (no residual: zero records)
+    const srsrc_t rs_R = make_srsrc(p.R, p.R ? p.ldr : (int64_t)kMlpH, p.E);        // (no residual: zero records)
     const srsrc_t rs_O = make_srsrc(p.out, p.ldo, p.E);
     {                                                         // the plain panel W2, 32 values per round trip
-      const rsrc_t rs_W = make_rsrc(p.W2, (uint32_t)(kHE * p.ldw2 * 4));
-      const uint32_t w_first = (uint32_t)(p.w2_transposed ? (int64_t)col * p.ldw2 + kHalfE * h : (int64_t)kHalfE * h * p.ldw2 + col) * 4u;
+      const rsrc_t rs_W = make_rsrc(p.W2, (uint32_t)(kMlpH * p.ldw2 * 4));
+      const uint32_t w_first = (uint32_t)(p.w2_transposed ? (int64_t)col * p.ldw2 + kMlpHalf * h : (int64_t)kMlpHalf * h * p.ldw2 + col) * 4u;
       const uint32_t w_step = __builtin_amdgcn_readfirstlane((int)(p.w2_transposed ? 4 : p.ldw2 * 4));
-      uint32_t off;
-      asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "v"(w_first));
-#pragma unroll
-      for (int s0 = 0; s0 < kHalfE; s0 += 32) {
-        float w0[32];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) w0[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_W, (int)off, (int)((s0 + j) * w_step), 0));
-#pragma unroll
-        for (int q = 0; q < 32; q += 8)
-          split8(make_float4(w0[q], w0[q + 1], w0[q + 2], w0[q + 3]), make_float4(w0[q + 4], w0[q + 5], w0[q + 6], w0[q + 7]), B6[(s0 + q) / 8]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      load_panel_x6(B6, rs_W, w_first, w_step);
     }
     float4 g1[4];
     auto fetch_residual = [&](int par, int q) {               // rows 8 q + lrow of the tile (a padding row, no residual: zeros)
@@ -332,9 +284,9 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
     int par = 0;
     for (int k = 0; k < mine; ++k) {
       lds_barrier();                                          // (barrier k+1) tile k's H1 image is complete
-      x6_tile(himg + (k & 1) * kTileD, [&](int) {});
-      acc_to_scr();
-      const int nxt = (par + 1) & (kRing - 1);
+      x6_tile(himg + (k & 1) * kMlpTile, [&](int) {});
+      acc_to_scr(scr, acc, h, li);
+      const int nxt = (par + 1) & (kMlpRing - 1);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int rr = 8 * q + lrow;
@@ -349,21 +301,9 @@ __global__ __launch_bounds__(kThreadsE, 1) void edge_mlp_k(const EdgeMlpArgs p) 
   }
 }
 
-inline unsigned edge_mlp_blocks(int64_t tiles_bound) {
-  const int64_t cap = 256;                                    // one workgroup per CU
-  return (unsigned)(tiles_bound < cap ? (tiles_bound > 0 ? tiles_bound : 1) : cap);
-}
-
-constexpr int kMaxDevicesE = 64;
 inline bool edge_mlp_lds_ready() {
-  static bool done[kMaxDevicesE] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesE) dev = 0;
-  if (done[dev]) return true;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&edge_mlp_k), hipFuncAttributeMaxDynamicSharedMemorySize, kEdgeMlpLdsBytes);
-  if (e != hipSuccess) { set_last_hip_error(e); return false; }
-  done[dev] = true;
-  return true;
+  static bool done[kMaxDevices] = {};
+  return opt_in_lds(reinterpret_cast<const void *>(&edge_mlp_k), kEdgeMlpLdsBytes, done);
 }
 
 }  // namespace
@@ -399,7 +339,7 @@ int dmp_edge_mlp_fwd(const float *Z, int64_t ldz, const float *W, int64_t ldw, c
   a.W2 = W2; a.ldw2 = ldw2; a.w2_transposed = w2_in_out ? 0 : 1; a.bias2 = bias2; a.R = R; a.ldr = R ? ldr : H;
   a.H1 = H1; a.ldh = ldh; a.out = out; a.ldo = ldo; a.E = E; a.slot_edge = slot_edge; a.tile_scale = tile_scale; a.num_tiles = num_tiles;
   a.slope = slope;
-  edge_mlp_k<<<edge_mlp_blocks(tiles_bound), kThreadsE, kEdgeMlpLdsBytes, (hipStream_t)stream>>>(a);
+  edge_mlp_k<<<one_per_cu_blocks(tiles_bound), kMlpThreads, kEdgeMlpLdsBytes, (hipStream_t)stream>>>(a);
   return check_launch();
 }
 

@@ -29,7 +29,7 @@
 // workgroup's prefetch depth already covers the fabric latency, so the second role rides in the other half of the SIMDs' slots.
 #include <type_traits>
 
-#include "dmp_mfma_common.h"
+#include "dmp_x6_tile.h"
 
 namespace dmp {
 namespace {
@@ -56,7 +56,6 @@ constexpr int kImgB = 2 * kOpB;                      // dO then H1: 98304
 constexpr int kScrB = 4 * 32 * kScrStride * 4;       // the row waves' accumulator transposes: 18432
 constexpr int kRowCB = 3 * kSub * 4;                 // store rows of three tiles in flight
 constexpr int kH1WLdsBytes = kImgB + kScrB + kRowCB; // 117120: dynamic LDS, opted in once per device
-constexpr int kMaxDevicesW2 = 64;
 
 typedef short v4s __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4s *lds_v4s_ptr;
@@ -215,20 +214,7 @@ __global__ __launch_bounds__(kThreadsW, 1) void h1w_k(const std::conditional_t<M
   Split8 B6[kGroups];                                    // the W2 panel's fragments of this wave's column slice, as bf16 pieces
   auto load_panel = [&]() {
     const rsrc_t rs_W = make_rsrc(p.W2, (uint32_t)(kHW * p.ldw * 4));
-    uint32_t off;
-    const uint32_t w_first = (uint32_t)((int64_t)64 * h * p.ldw + col) * 4u;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "v"(w_first));
-    const uint32_t w_step = __builtin_amdgcn_readfirstlane((int)(p.ldw * 4));
-#pragma unroll
-    for (int s0 = 0; s0 < 64; s0 += 32) {
-      float w0[32];
-#pragma unroll
-      for (int j = 0; j < 32; ++j) w0[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_W, (int)off, (int)((s0 + j) * w_step), 0));
-#pragma unroll
-      for (int q = 0; q < 32; q += 8)
-        split8(make_float4(w0[q], w0[q + 1], w0[q + 2], w0[q + 3]), make_float4(w0[q + 4], w0[q + 5], w0[q + 6], w0[q + 7]), B6[(s0 + q) / 8]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    load_panel_x6(B6, rs_W, (uint32_t)((int64_t)64 * h * p.ldw + col) * 4u, __builtin_amdgcn_readfirstlane((int)(p.ldw * 4)));
   };
   // row read of the A operand: row li, chunk 8 h + g  ->  256 li + 16 ((8 h + g) ^ swz(li)) = a0 ^ (16 g)
   const uint32_t a0 = 256u * (uint32_t)li + 16u * ((uint32_t)(8 * h) ^ swz((uint32_t)li));
@@ -766,14 +752,8 @@ inline unsigned atb2_blocks(int64_t tiles_bound, int num_jobs) {
 }
 
 inline bool atb2_lds_ready() {
-  static bool done[kMaxDevicesW2] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesW2) dev = 0;
-  if (done[dev]) return true;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&atb2_k), hipFuncAttributeMaxDynamicSharedMemorySize, kAtb2LdsBytes);
-  if (e != hipSuccess) { set_last_hip_error(e); return false; }
-  done[dev] = true;
-  return true;
+  static bool done[kMaxDevices] = {};
+  return opt_in_lds(reinterpret_cast<const void *>(&atb2_k), kAtb2LdsBytes, done);
 }
 
 
@@ -1133,33 +1113,16 @@ __global__ __launch_bounds__(kThreadsW, 1) void dzw_k(const DzwArgs p) {
 
 constexpr int kDzwLdsBytes = kImgB + kScrB + 4 * 3 * kSub * 4;
 inline bool dzw_lds_ready() {
-  static bool done[kMaxDevicesW2] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesW2) dev = 0;
-  if (done[dev]) return true;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&dzw_k), hipFuncAttributeMaxDynamicSharedMemorySize, kDzwLdsBytes);
-  if (e != hipSuccess) { set_last_hip_error(e); return false; }
-  done[dev] = true;
-  return true;
+  static bool done[kMaxDevices] = {};
+  return opt_in_lds(reinterpret_cast<const void *>(&dzw_k), kDzwLdsBytes, done);
 }
 
-inline unsigned h1w_blocks(int64_t tiles_bound) {
-  const int64_t cap = 256;                               // one workgroup per CU
-  return (unsigned)(tiles_bound < cap ? (tiles_bound > 0 ? tiles_bound : 1) : cap);
-}
+inline unsigned h1w_blocks(int64_t tiles_bound) { return one_per_cu_blocks(tiles_bound); }
 
-constexpr int kMaxDevicesW = 64;
 template <int MODE>
 inline bool h1w_lds_ready() {
-  static bool done[kMaxDevicesW] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesW) dev = 0;
-  if (done[dev]) return true;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&h1w_k<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           MODE == 0 ? kH1WLdsBytes : kH1WCodesLdsBytes);
-  if (e != hipSuccess) { set_last_hip_error(e); return false; }
-  done[dev] = true;
-  return true;
+  static bool done[kMaxDevices] = {};
+  return opt_in_lds(reinterpret_cast<const void *>(&h1w_k<MODE>), MODE == 0 ? kH1WLdsBytes : kH1WCodesLdsBytes, done);
 }
 
 // dmp_bwd_h1_w's argument checks (both entries); DMP_OK: launch

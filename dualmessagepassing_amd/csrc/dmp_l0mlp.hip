@@ -25,7 +25,7 @@
 // 16-wide code image are written between k-2 and k-1 and last read between k+1 and k+2, while tile k+3's are written: rings of four.
 #include <type_traits>
 
-#include "dmp_mfma_common.h"
+#include "dmp_x6_tile.h"
 
 namespace dmp {
 namespace {
@@ -50,10 +50,7 @@ struct L0MlpArgs {
   float slope;
 };
 
-constexpr int kHL = 128, kThreadsL = 512;
-constexpr int kStrideL = (kHL + 8) / 2;             // dwords per H1 image row: 128 bf16 + 8 of padding
-constexpr int kPlaneL = kSub * kStrideL;
-constexpr int kTileL = 3 * kPlaneL;                 // hi | mid | lo: 26112 bytes
+// (the workgroup's geometry and the H1 image's -- kMlpThreads, kMlpStride / kMlpPlane / kMlpTile, kMlpRing -- are dmp_x6_tile.h's, shared with edge_mlp_k)
 constexpr int kSlot = 12;                           // code columns per operand slot: K <= kSlot
 constexpr int kOpGroups = 4 * kSlot / 16;           // 16-deep k-groups of the first role's product (3)
 constexpr int kOpStride = (4 * kSlot + 8) / 2;      // dwords per operand row: 48 bf16 + 8 of padding (28: rows of whole 16-byte pieces)
@@ -61,22 +58,20 @@ constexpr int kOpPlane = kSub * kOpStride;
 constexpr int kOpTile = 3 * kOpPlane;               // 10752 bytes
 constexpr int kCxPlane = kSub * 8;                  // the second role's code rows: 16 bf16 per row and plane
 constexpr int kCxTile = 3 * kCxPlane;               // 3072 bytes
-constexpr int kRingL = 4;                           // tiles whose row indices / code images are alive at once
-constexpr int kOpOff = 2 * kTileL * 4;              // behind the H1 image's two buffers
+constexpr int kOpOff = 2 * kMlpTile * 4;            // behind the H1 image's two buffers
 constexpr int kCxOff = kOpOff + 2 * kOpTile * 4;
-constexpr int kScrOffL = kCxOff + kRingL * kCxTile * 4;
+constexpr int kScrOffL = kCxOff + kMlpRing * kCxTile * 4;
 constexpr int kRowsOffL = kScrOffL + 8 * 32 * kScrStride * 4;
-constexpr int kL0MlpLdsBytes = kRowsOffL + 3 * kRingL * kSub * 4;   // 52224 + 21504 + 12288 + 36864 + 1536 = 124416
-constexpr int kHalfL = kHL / 2, kGroupsL = kHalfL / 8;
+constexpr int kL0MlpLdsBytes = kRowsOffL + 3 * kMlpRing * kSub * 4;   // 52224 + 21504 + 12288 + 36864 + 1536 = 124416
 static_assert(4 * kSlot % 16 == 0 && kOpStride % 4 == 0, "whole k-groups, 16-byte fragment reads");
 
-__global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p) {
+__global__ __launch_bounds__(kMlpThreads, 1) void l0_edge_mlp_k(const L0MlpArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   uint32_t *const himg = reinterpret_cast<uint32_t *>(lds);
   uint32_t *const opimg = reinterpret_cast<uint32_t *>(lds + kOpOff);
   uint32_t *const cximg = reinterpret_cast<uint32_t *>(lds + kCxOff);
-  uint32_t *const rowA = reinterpret_cast<uint32_t *>(lds + kRowsOffL);           // [kRingL][32] each: row INDICES (-1: none)
-  uint32_t *const rowB = rowA + kRingL * kSub, *const rowC = rowB + kRingL * kSub;
+  uint32_t *const rowA = reinterpret_cast<uint32_t *>(lds + kRowsOffL);           // [kMlpRing][32] each: row INDICES (-1: none)
+  uint32_t *const rowB = rowA + kMlpRing * kSub, *const rowC = rowB + kMlpRing * kSub;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const bool second = wave >= 4;
   const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5, cs = wave & 3;
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
   float *const scr = reinterpret_cast<float *>(lds + kScrOffL) + wave * (32 * kScrStride);
   const int lrow = lane >> 3, c4 = 32 * cs + (lane & 7) * 4;
   const uint32_t col4 = (uint32_t)c4 * 4u;
-  constexpr uint32_t kRowBytes = kHL * 4u;
+  constexpr uint32_t kRowBytes = kMlpH * 4u;
   constexpr uint32_t kNone = 0xFFFFFFFFu, kOOB = 0xFFFFF000u;
 
   // this workgroup's contiguous tile range
@@ -96,16 +91,8 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
   const int mine = hi > lo ? hi - lo : 0;
   if (mine == 0) return;                                                          // (uniform per workgroup: before any barrier)
 
-  Split8 B6[kGroupsL];                    // the role's panel as bf16 pieces (the first role: kOpGroups fragments of it)
+  Split8 B6[kMlpGroups];                    // the role's panel as bf16 pieces (the first role: kOpGroups fragments of it)
   f32x16 acc;
-  auto six = [&](const Frag8 &ah, const Frag8 &am, const Frag8 &al, const Split8 &bb) {   // the small terms first (mfma_x6's order)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al.v, bb.hi.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.lo.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am.v, bb.mid.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am.v, bb.hi.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.mid.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.hi.v, acc, 0, 0, 0);
-  };
   // A tile's product on the bf16 pipe: per 16-deep k-group g six MFMAs on the three piece fragments of image row li (this lane's 8
   // consecutive k: `first` + `step` g dwords into the row, one ds_read_b128 per plane, requested one group ahead) and B6[g].
   auto x6_tile = [&](const uint32_t *ar, int plane, int step, auto groups) {
@@ -125,14 +112,10 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
         nl.v = *reinterpret_cast<const bf16x8 *>(ar + 2 * plane + step * (g + 1));
       }
       __builtin_amdgcn_sched_barrier(0);
-      six(ah, am, al, B6[g]);
+      acc = mfma_x6(ah, am, al, B6[g], acc);
       __builtin_amdgcn_sched_barrier(0);
       ah = nh; am = nm; al = nl;
     }
-  };
-  auto acc_to_scr = [&]() {                // the accumulator block through this wave's scratch: rows of 4 consecutive columns per lane
-#pragma unroll
-    for (int r = 0; r < 16; ++r) scr[((r & 3) + 8 * (r >> 2) + 4 * h) * kScrStride + li] = acc[r];
   };
 
   if (!second) {
@@ -164,7 +147,7 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
         for (int j = 0; j < 8; ++j) {
           const int k = 16 * g + 8 * h + j, s = k / kSlot, jj = k - s * kSlot, t = s & 1, half = s >> 1;
           const bool ok = jj < K && t < p.tables;                                  // (a slot's columns >= K, a table not there: zeros)
-          const uint32_t off = ok ? (uint32_t)(((int64_t)(t * K + jj) * p.ldm + half * kHL + col) * 4) : kOOB;
+          const uint32_t off = ok ? (uint32_t)(((int64_t)(t * K + jj) * p.ldm + half * kMlpH + col) * 4) : kOOB;
           w[g][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_M, (int)off, 0, 0));
         }
       }
@@ -244,9 +227,9 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
       g1[k] = sbuf_load4(rs_T, (int)rowB[par * kSub + rr], col4 + kRowBytes);
     };
     auto epilogue = [&](int k, int par) {
-      uint32_t *const img = himg + (k & 1) * kTileL;
-      const int nxt = (par + 1) & (kRingL - 1);
-      acc_to_scr();
+      uint32_t *const img = himg + (k & 1) * kMlpTile;
+      const int nxt = (par + 1) & (kMlpRing - 1);
+      acc_to_scr(scr, acc, h, li);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int rr = 8 * q + lrow;
@@ -262,10 +245,10 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
         uint2 ph, pm, pl;
         split_pair(pad ? 0.f : v.x, pad ? 0.f : v.y, ph.x, pm.x, pl.x);
         split_pair(pad ? 0.f : v.z, pad ? 0.f : v.w, ph.y, pm.y, pl.y);
-        uint32_t *w = img + rr * kStrideL + (c4 >> 1);
+        uint32_t *w = img + rr * kMlpStride + (c4 >> 1);
         *reinterpret_cast<uint2 *>(w) = ph;
-        *reinterpret_cast<uint2 *>(w + kPlaneL) = pm;
-        *reinterpret_cast<uint2 *>(w + 2 * kPlaneL) = pl;
+        *reinterpret_cast<uint2 *>(w + kMlpPlane) = pm;
+        *reinterpret_cast<uint2 *>(w + 2 * kMlpPlane) = pl;
         // this chunk's operand registers are free: request the NEXT tile's rows into them (its indices were staged during
         // this tile's MFMA phase, before the barrier); past the last tile they are out of range: zeros
         fetch_operand(nxt, q);
@@ -283,8 +266,8 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
 #pragma unroll
     for (int c = 0; c < 4; ++c) fetch_operand(0, c);          // tile 0's epilogue operands (later tiles: by the epilogue before)
     for (int k = 0; k < mine; ++k) {
-      const int par = k & (kRingL - 1);
-      stage((k + 1) & 1, (par + 1) & (kRingL - 1));           // tile k+1 (past the end: zeros, no rows)
+      const int par = k & (kMlpRing - 1);
+      stage((k + 1) & 1, (par + 1) & (kMlpRing - 1));           // tile k+1 (past the end: zeros, no rows)
       load_data();                                            // tile k+2
       load_ids(k + 3);
       x6_tile(opimg + (k & 1) * kOpTile + li * kOpStride + 4 * h, kOpPlane, 8, std::integral_constant<int, kOpGroups>());
@@ -296,7 +279,7 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
     // ==================================================================== the second Linear (waves 4-7): mfma_typed_codes
     __builtin_amdgcn_s_setprio(1);                            // the later-dispatched half loses every arbitration otherwise
     const float4 bias4 = buf_load4(make_rsrc(p.bias2, p.bias2 ? kRowBytes : 0u), col4, 0);   // (no bias: zero records -> zeros, no branch)
-    const srsrc_t rs_R = make_srsrc(p.R, p.R ? p.ldr : (int64_t)kHL, p.r_rows);   // (no residual, rows >= r_rows: zero records)
+    const srsrc_t rs_R = make_srsrc(p.R, p.R ? p.ldr : (int64_t)kMlpH, p.r_rows);   // (no residual, rows >= r_rows: zero records)
     const srsrc_t rs_O = make_srsrc(p.out, p.ldo, p.E);
     Split8 BX;                                                // the codes k-group's panel fragment: BX[j] = Wc[8 h + j][col]
     {
@@ -306,22 +289,10 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
       for (int j = 0; j < 8; ++j)
         w[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_Wc, (int)(((int64_t)(8 * h + j) * p.ldwc + col) * 4), 0, 0));
       // the plain panel W2, 32 values per round trip
-      const rsrc_t rs_W = make_rsrc(p.W2, (uint32_t)(kHL * p.ldw2 * 4));
-      const uint32_t w_first = (uint32_t)(p.w2_transposed ? (int64_t)col * p.ldw2 + kHalfL * h : (int64_t)kHalfL * h * p.ldw2 + col) * 4u;
+      const rsrc_t rs_W = make_rsrc(p.W2, (uint32_t)(kMlpH * p.ldw2 * 4));
+      const uint32_t w_first = (uint32_t)(p.w2_transposed ? (int64_t)col * p.ldw2 + kMlpHalf * h : (int64_t)kMlpHalf * h * p.ldw2 + col) * 4u;
       const uint32_t w_step = __builtin_amdgcn_readfirstlane((int)(p.w2_transposed ? 4 : p.ldw2 * 4));
-      uint32_t off;
-      asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "v"(w_first));
-#pragma unroll
-      for (int s0 = 0; s0 < kHalfL; s0 += 32) {
-        float w0[32];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) w0[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_W, (int)off, (int)((s0 + j) * w_step), 0));
-        if (s0 == 0) split8(make_float4(w[0], w[1], w[2], w[3]), make_float4(w[4], w[5], w[6], w[7]), BX);
-#pragma unroll
-        for (int q = 0; q < 32; q += 8)
-          split8(make_float4(w0[q], w0[q + 1], w0[q + 2], w0[q + 3]), make_float4(w0[q + 4], w0[q + 5], w0[q + 6], w0[q + 7]), B6[(s0 + q) / 8]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      load_panel_x6(B6, rs_W, w_first, w_step, [&] { split8(make_float4(w[0], w[1], w[2], w[3]), make_float4(w[4], w[5], w[6], w[7]), BX); });
     }
     float4 g1[4];
     auto fetch_residual = [&](int par, int q) {               // rows 8 q + lrow of the tile (padding, rows >= r_rows, no residual: zeros)
@@ -332,18 +303,18 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
     for (int q = 0; q < 4; ++q) fetch_residual(0, q);
     lds_barrier();                                            // (barrier 0)
     for (int k = 0; k < mine; ++k) {
-      const int par = k & (kRingL - 1), nxt = (par + 1) & (kRingL - 1);
+      const int par = k & (kMlpRing - 1), nxt = (par + 1) & (kMlpRing - 1);
       lds_barrier();                                          // (barrier k+1) tile k's H1 image is complete
-      x6_tile(himg + (k & 1) * kTileL + li * kStrideL + (kHalfL / 2) * h, kPlaneL, 4, std::integral_constant<int, kGroupsL>());
+      x6_tile(himg + (k & 1) * kMlpTile + li * kMlpStride + (kMlpHalf / 2) * h, kMlpPlane, 4, std::integral_constant<int, kMlpGroups>());
       {                                                       // + codes Wc: one more 16-deep k-group (this lane: codes 8 h .. 8 h + 7 of row li)
         const uint32_t *c = cximg + par * kCxTile + li * 8 + 4 * h;
         Frag8 ch, cm, cl;
         ch.v = *reinterpret_cast<const bf16x8 *>(c);
         cm.v = *reinterpret_cast<const bf16x8 *>(c + kCxPlane);
         cl.v = *reinterpret_cast<const bf16x8 *>(c + 2 * kCxPlane);
-        six(ch, cm, cl, BX);
+        acc = mfma_x6(ch, cm, cl, BX, acc);
       }
-      acc_to_scr();
+      acc_to_scr(scr, acc, h, li);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int rr = 8 * q + lrow;
@@ -357,21 +328,9 @@ __global__ __launch_bounds__(kThreadsL, 1) void l0_edge_mlp_k(const L0MlpArgs p)
   }
 }
 
-inline unsigned l0_mlp_blocks(int64_t tiles_bound) {
-  const int64_t cap = 256;                                    // one workgroup per CU
-  return (unsigned)(tiles_bound < cap ? (tiles_bound > 0 ? tiles_bound : 1) : cap);
-}
-
-constexpr int kMaxDevicesL = 64;
 inline bool l0_mlp_lds_ready() {
-  static bool done[kMaxDevicesL] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesL) dev = 0;
-  if (done[dev]) return true;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&l0_edge_mlp_k), hipFuncAttributeMaxDynamicSharedMemorySize, kL0MlpLdsBytes);
-  if (e != hipSuccess) { set_last_hip_error(e); return false; }
-  done[dev] = true;
-  return true;
+  static bool done[kMaxDevices] = {};
+  return opt_in_lds(reinterpret_cast<const void *>(&l0_edge_mlp_k), kL0MlpLdsBytes, done);
 }
 
 }  // namespace
@@ -412,7 +371,7 @@ int dmp_l0_edge_mlp_fwd(const float *enc, int64_t lde, int K, const float *M, in
   a.W2 = W2; a.ldw2 = ldw2; a.w2_transposed = w2_in_out ? 0 : 1; a.bias2 = bias2; a.Wc = Wc; a.ldwc = ldwc; a.code_row0 = code_row0;
   a.R = R; a.ldr = R ? ldr : H; a.r_rows = R ? r_rows : 0; a.H1 = H1; a.ldh = ldh; a.out = out; a.ldo = ldo; a.E = E;
   a.slot_edge = slot_edge; a.num_tiles = num_tiles; a.slope = slope;
-  l0_edge_mlp_k<<<l0_mlp_blocks(tiles_bound), kThreadsL, kL0MlpLdsBytes, (hipStream_t)stream>>>(a);
+  l0_edge_mlp_k<<<one_per_cu_blocks(tiles_bound), kMlpThreads, kL0MlpLdsBytes, (hipStream_t)stream>>>(a);
   return check_launch();
 }
 

@@ -178,15 +178,6 @@ __global__ __launch_bounds__(kGroupThreads, 2) void l0_node_mfma_k(const L0NodeA
     if (sc == 0) rowid[buf * kSub + srow] = id_data;
   };
 
-  auto six = [&](f32x16 &c, const Frag8 &ah, const Frag8 &am, const Frag8 &al, const Split8 &bb) {   // the small terms first (mfma_x6's order)
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al.v, bb.hi.v, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.lo.v, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am.v, bb.mid.v, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am.v, bb.hi.v, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.mid.v, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.hi.v, c, 0, 0, 0);
-  };
-
   for (int k = 0; k < mine; ++k) {
     const int buf = k & 1;
     stage(buf, pre_a, pre_b, id_data);                                             // tile k
@@ -225,7 +216,7 @@ __global__ __launch_bounds__(kGroupThreads, 2) void l0_node_mfma_k(const L0NodeA
 #pragma unroll
             for (int d = 0; d < 4; ++d) M[pl].u[d] = on ? A[g][pl].u[d] : 0u;
           }
-          six(acc, M[0], M[1], M[2], B[b == 0 ? g : b + 2]);
+          acc = mfma_x6(M[0], M[1], M[2], B[b == 0 ? g : b + 2], acc);
         }
       };
       if (has0) product(BW[0], in0);                                               // (wave-uniform, around MFMAs only)

@@ -61,16 +61,18 @@ __device__ __forceinline__ void split8(const float4 &x, const float4 &y, Split8 
   split_pair(y.x, y.y, s.hi.u[2], s.mid.u[2], s.lo.u[2]);
   split_pair(y.z, y.w, s.hi.u[3], s.mid.u[3], s.lo.u[3]);
 }
-// acc += A B for a 32x32x16 block given as pieces; the small terms first
-__device__ __forceinline__ f32x16 mfma_x6(const Split8 &a, const Split8 &b, f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.lo.v, b.hi.v, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi.v, b.lo.v, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.mid.v, b.mid.v, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.mid.v, b.hi.v, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi.v, b.mid.v, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi.v, b.hi.v, acc, 0, 0, 0);
+// acc += A B for a 32x32x16 block given as pieces; the small terms first.  A's pieces as loose fragments (a kernel that reads
+// them from an LDS image one k-group ahead has no Split8 to hand), or as a Split8.
+__device__ __forceinline__ f32x16 mfma_x6(const Frag8 &ah, const Frag8 &am, const Frag8 &al, const Split8 &b, f32x16 acc) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al.v, b.hi.v, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, b.lo.v, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am.v, b.mid.v, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am.v, b.hi.v, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, b.mid.v, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, b.hi.v, acc, 0, 0, 0);
   return acc;
 }
+__device__ __forceinline__ f32x16 mfma_x6(const Split8 &a, const Split8 &b, f32x16 acc) { return mfma_x6(a.hi, a.mid, a.lo, b, acc); }
 
 // ---- structured buffer access: address = base + index * stride + offset, the descriptor holds the row stride in bytes
 // (<= 16383) and the number of rows; a row index beyond it (e.g. -1) reads zeros / drops the store, and no multiply is

@@ -378,17 +378,10 @@ inline unsigned chain_blocks(int64_t tiles_bound) {
   return (unsigned)(want < 1 ? 1 : (want > kChainMaxBlocks ? kChainMaxBlocks : want));
 }
 
-constexpr int kMaxDevicesC = 64;
 template <bool BWD, bool FULL>
 inline bool chain_lds_ready() {
-  static bool done[kMaxDevicesC] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesC) dev = 0;
-  if (done[dev]) return true;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&node_chain_k<BWD, FULL>), hipFuncAttributeMaxDynamicSharedMemorySize, kChainLdsBytes);
-  if (e != hipSuccess) { set_last_hip_error(e); return false; }
-  done[dev] = true;
-  return true;
+  static bool done[kMaxDevices] = {};
+  return opt_in_lds(reinterpret_cast<const void *>(&node_chain_k<BWD, FULL>), kChainLdsBytes, done);
 }
 
 inline bool chain_rows_ok(const float *a, int64_t ld, int64_t rows) {

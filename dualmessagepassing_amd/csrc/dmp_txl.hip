@@ -403,17 +403,6 @@ __global__ void __launch_bounds__(kBlock) txl_bwd_k(TxlArgs a, const float *__re
   }
 }
 
-constexpr int kMaxDevicesT = 64;
-template <typename K> bool txl_lds_ready(K kernel, bool (&done)[kMaxDevicesT], int bytes) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevicesT) dev = 0;
-  if (done[dev]) return true;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) { set_last_hip_error(e); return false; }
-  done[dev] = true;
-  return true;
-}
-
 bool txl_shape_ok(int q, int k, int dh) {
   return q >= 1 && q <= kTxlMaxQ && k >= q && k <= kTxlMaxK && (dh == 16 || dh == 32 || dh == 64 || dh == 128);
 }
@@ -425,9 +414,9 @@ int txl_groups(int64_t N, int nh) {
 
 template <int DC>
 int txl_fwd_launch(const TxlArgs &a, float *O, float *rmax, float *rsum, hipStream_t st) {
-  static bool done[kMaxDevicesT] = {};
+  static bool done[kMaxDevices] = {};
   constexpr int kMaxBytes = 4 * txl_lds_floats<DC>(kTxlMaxQ, kTxlMaxK, 1, 2);
-  if (!txl_lds_ready(&txl_fwd_k<DC>, done, kMaxBytes)) return DMP_ERR_HIP;
+  if (!opt_in_lds(reinterpret_cast<const void *>(&txl_fwd_k<DC>), kMaxBytes, done)) return DMP_ERR_HIP;
   const size_t bytes = sizeof(float) * (size_t)txl_lds_floats<DC>(a.q, a.k, 1, 2);
   txl_fwd_k<DC><<<(unsigned)(a.N * a.nh), kBlock, bytes, st>>>(a, O, rmax, rsum);
   return check_launch();
@@ -436,9 +425,9 @@ int txl_fwd_launch(const TxlArgs &a, float *O, float *rmax, float *rsum, hipStre
 template <int DC>
 int txl_bwd_launch(const TxlArgs &a, const float *dO, const float *rmax, const float *rsum, float *dQ, float *dK, float *dV,
                    float *partial, hipStream_t st) {
-  static bool done[kMaxDevicesT] = {};
+  static bool done[kMaxDevices] = {};
   constexpr int kMaxBytes = 4 * txl_lds_floats<DC>(kTxlMaxQ, kTxlMaxK, 2, 3);
-  if (!txl_lds_ready(&txl_bwd_k<DC>, done, kMaxBytes)) return DMP_ERR_HIP;
+  if (!opt_in_lds(reinterpret_cast<const void *>(&txl_bwd_k<DC>), kMaxBytes, done)) return DMP_ERR_HIP;
   const size_t bytes = sizeof(float) * (size_t)txl_lds_floats<DC>(a.q, a.k, 2, 3);
   const int groups = txl_groups(a.N, a.nh);
   txl_bwd_k<DC><<<(unsigned)(groups * a.nh), kBlock, bytes, st>>>(a, dO, rmax, rsum, groups, dQ, dK, dV, partial);

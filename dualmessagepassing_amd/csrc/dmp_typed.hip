@@ -17,7 +17,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "dmp_mfma_common.h"
+#include "dmp_x6_tile.h"
 
 namespace dmp {
 namespace {
@@ -305,50 +305,16 @@ __device__ __forceinline__ void typed_body(const TypedArgs &p) {
   // lane's 8 consecutive k = kHalf h + 8g .. of row li: one ds_read_b128 per plane, requested one group ahead) and the
   // panel fragment B6[g]; the caller's 16 actions (requests / staging of the neighbouring tiles) are spread between them.
   auto x6_tile = [&](const float *tile, auto &&action) {
-    constexpr int kPer = 16 / kGroups;                      // actions per group: 2 (H = 128) or 4 (H = 64)
-    const uint32_t *ar = reinterpret_cast<const uint32_t *>(tile) + li * kStrideD + (kHalf / 2) * h;
-    Frag8 ah, am, al;
-    ah.v = *reinterpret_cast<const bf16x8 *>(ar);
-    am.v = *reinterpret_cast<const bf16x8 *>(ar + kPlane);
-    al.v = *reinterpret_cast<const bf16x8 *>(ar + 2 * kPlane);
-#pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-      Frag8 nh = ah, nm = am, nl = al;
-      if (g + 1 < kGroups) {
-        nh.v = *reinterpret_cast<const bf16x8 *>(ar + 4 * (g + 1));
-        nm.v = *reinterpret_cast<const bf16x8 *>(ar + kPlane + 4 * (g + 1));
-        nl.v = *reinterpret_cast<const bf16x8 *>(ar + 2 * kPlane + 4 * (g + 1));
-      }
-      const Split8 &bb = B6[X6 ? g : 0];
-      int done = 0;
-      auto after = [&](int n) {                             // the actions due after the n-th MFMA of the group
-#pragma unroll
-        for (int q = 0; q < kPer; ++q)
-          if (6 * (q + 1) / kPer == n) { action(kPer * g + q); ++done; }
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      __builtin_amdgcn_sched_barrier(0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al.v, bb.hi.v, acc, 0, 0, 0); after(1);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.lo.v, acc, 0, 0, 0); after(2);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am.v, bb.mid.v, acc, 0, 0, 0); after(3);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am.v, bb.hi.v, acc, 0, 0, 0); after(4);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.mid.v, acc, 0, 0, 0); after(5);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bb.hi.v, acc, 0, 0, 0); after(6);
-      (void)done;
-      ah = nh; am = nm; al = nl;
-    }
+    // (!X6: B6 has ONE element and this lambda is instantiated all the same -- the template then indexes B6[g] beyond it, in code that
+    // never runs: every call of x6_tile stands under `if (X6)`.  An `if constexpr (X6)` here changes the file's device assembly.)
+    x6_kgroups_fenced<kGroups>(PaddedRowRead<kPlane>{reinterpret_cast<const uint32_t *>(tile) + li * kStrideD + (kHalf / 2) * h}, B6, acc, action);
     if (CODES) {                                             // + codes Wc: one more 16-deep k-group (this lane: codes 8 h .. 8 h + 7 of row li)
       const int cb = (tile == &As[0][0]) ? 0 : 1;
       Frag8 ch, cm, cl;
       ch.v = *reinterpret_cast<const bf16x8 *>(&Cx[CODES ? cb : 0][0][li * 8 + 4 * h]);
       cm.v = *reinterpret_cast<const bf16x8 *>(&Cx[CODES ? cb : 0][1][li * 8 + 4 * h]);
       cl.v = *reinterpret_cast<const bf16x8 *>(&Cx[CODES ? cb : 0][2][li * 8 + 4 * h]);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cl.v, BX.hi.v, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch.v, BX.lo.v, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cm.v, BX.mid.v, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cm.v, BX.hi.v, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch.v, BX.mid.v, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ch.v, BX.hi.v, acc, 0, 0, 0);
+      acc = mfma_x6(ch, cm, cl, BX, acc);
     }
   };
   // The MFMA phase, with the epilogue operand requests of the same tile in its shadow: two of the eight loads
