@@ -28,14 +28,18 @@ LEAKY_RELU_A = 1 / 5.5  # constants.py:10
 KINKED = ("relu", "leaky_relu")  # activations whose derivative jumps at 0
 
 
+NEGATIVE_SLOPE = {"relu": 0.0, "leaky_relu": LEAKY_RELU_A}  # the derivative left of the kink
+
+
 def activation(name):
     # utils/act.py:457-474
     fn = _activation(name)
+    act = lambda x: fn(x)
     if name in KINKED:
-        return fn
-    smooth = lambda x: fn(x)
-    smooth.smooth = True          # the probe below records "no kink here" for these
-    return smooth
+        act.slope = NEGATIVE_SLOPE[name]   # the pin below needs the other branch's derivative
+    else:
+        act.smooth = True         # the probe below records "no kink here" for these
+    return act
 
 
 def _activation(name):
@@ -61,6 +65,54 @@ def probe(site, pre, act=None):
         # a smooth activation has no ambiguous elements: its layer is still recorded (the tracing needs every layer)
         PROBE.append((site, th.full_like(pre[:, :1], float("inf")) if getattr(act, "smooth", False) else pre.detach()))
     return pre
+
+
+# Test hook: when a list of bool tensors, one per piecewise-linear activation site in evaluation order, the activation at
+# that site keeps its forward value and takes its DERIVATIVE from the mask: 1 where True, the negative slope elsewhere.  The
+# run is then the exact gradient of the piecewise-linear function whose branches the masks name -- the branches a product
+# took, read from the hidden rows it keeps for its own backward (tests/util_branches.py).  ``pinned`` installs the list and
+# checks that every entry was used; a smooth activation takes no entry.  With PIN None the arithmetic is untouched.
+PIN = None
+_PIN_USED = 0
+
+
+class pinned:
+    """``with pinned(masks): ...`` -- the oracle forward inside runs on the derivative branches of ``masks``."""
+
+    def __init__(self, masks):
+        self.masks = list(masks)
+
+    def __enter__(self):
+        global PIN, _PIN_USED
+        if PIN is not None:
+            raise RuntimeError("the oracle is pinned already")
+        PIN, _PIN_USED = self.masks, 0
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        global PIN, _PIN_USED
+        used, PIN, _PIN_USED = _PIN_USED, None, 0
+        if exc_type is None and used != len(self.masks):
+            raise ValueError("%d branch masks pinned, the oracle evaluated %d kinked activation sites" % (len(self.masks), used))
+        return False
+
+
+def act_at(site, pre, act):
+    """``act(pre)`` at a recorded activation site: probed, and under ``PIN`` with the derivative of the next mask."""
+    global _PIN_USED
+    pre = probe(site, pre, act)
+    if PIN is None or getattr(act, "smooth", False):
+        return act(pre)
+    if _PIN_USED >= len(PIN):
+        raise ValueError("site %d (%s): only %d branch masks pinned" % (_PIN_USED, site, len(PIN)))
+    mask = PIN[_PIN_USED]
+    if mask.dtype != th.bool or tuple(mask.shape) != tuple(pre.shape):
+        raise ValueError("site %d (%s): mask %s %s for a pre-activation of shape %s" % (
+            _PIN_USED, site, mask.dtype, tuple(mask.shape), tuple(pre.shape)))
+    _PIN_USED += 1
+    d = th.where(mask.to(pre.device), th.ones((), dtype=pre.dtype, device=pre.device),
+                 th.full((), act.slope, dtype=pre.dtype, device=pre.device))
+    return act(pre).detach() + d * (pre - pre.detach())
 
 
 def seg_sum(msg, dst, num_nodes):
@@ -91,7 +143,7 @@ def mlp(x, params, prefix, act, num_layers=2, bn=None, training=False):
                 x = F.batch_norm(x, b["running_mean"], b["running_var"], params["%s.%d.weight" % (prefix, idx)],
                                  params["%s.%d.bias" % (prefix, idx)], training, 0.1, 1e-5)
                 idx += 1
-            x = act(probe(prefix, x, act))
+            x = act_at(prefix, x, act)
             idx += 1
     return x
 

@@ -82,11 +82,11 @@ def _head(sd, prefix, act, p_out, p_mask, g_out, g_mask, pool, return_weights):
     if return_weights:
         pe = p.unsqueeze(1).expand(bsz, g_len, -1)
         ple, plie = pl.expand(bsz, g_len).unsqueeze(-1), (1.0 / pl).expand(bsz, g_len).unsqueeze(-1)
-        w = act(O.probe(prefix + ".weight_fc1", lin("weight_fc1", th.cat([pe, g_rows, g_rows - pe, g_rows * pe, ple, plie], 2))))
+        w = O.act_at(prefix + ".weight_fc1", lin("weight_fc1", th.cat([pe, g_rows, g_rows - pe, g_rows * pe, ple, plie], 2)), act)
         w = lin("weight_fc2", th.cat([w, ple, plie], 2)).squeeze(-1)
     g = agg(g_rows)
     y = th.cat([p, g, g - p, g * p, pl, gl, 1.0 / pl, 1.0 / gl], 1)
-    y = act(O.probe(prefix + ".pred_fc1", lin("pred_fc1", y)))
+    y = O.act_at(prefix + ".pred_fc1", lin("pred_fc1", y), act)
     return lin("pred_fc2", th.cat([y, pl, gl, 1.0 / pl, 1.0 / gl], 1)), w
 
 
@@ -94,7 +94,9 @@ def model_forward(sd, cfg, pattern, graph):
     """``GraphAdjModelV2.forward`` (basemodel.py:1493-1661) of a DMPNN model.  ``sd``: reference ``state_dict``;
     ``cfg``: its construction kwargs (the keys read below); ``pattern`` / ``graph``: dicts with ``src``, ``dst``
     (global ids, eid order), ``bnn``, ``bne`` (per-graph sizes), ``id``, ``label`` (nodes), ``eid``, ``elabel``,
-    ``rev`` (edges; ``rev`` may be None).  Returns the 15-entry output dict."""
+    ``rev`` (edges; ``rev`` may be None).  Returns the 15-entry output dict, and beside it ``g_v_gate`` / ``g_e_gate``: the
+    0 / 1 filter gates applied to the target's node / edge rows ([N, 1] / [E, 1]; None without a filter net) -- a row under
+    a zero takes no gradient, which is what a check of the live rows needs to know."""
     act_rep = cfg.get("rep_act_func", "relu")
     act_pred = O.activation(cfg.get("pred_act_func", "relu"))
     node_pred, edge_pred = cfg.get("node_pred", True), cfg.get("edge_pred", True)
@@ -167,4 +169,5 @@ def model_forward(sd, cfg, pattern, graph):
         pred_c = v_c if node_pred else e_c
     out.update(masks)
     out.update(pred_c=pred_c, pred_v=v_w, pred_e=e_w)
+    out.update(g_v_gate=gates[0], g_e_gate=gates[1])
     return out
