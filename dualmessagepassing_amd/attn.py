@@ -41,7 +41,8 @@ def attention_tensor(q, k, v, qmask, kmask, num_heads, scale):
     """q [B, Lq, nh * dh], k / v [B, Lk, nh * dh], masks [B, L] (nonzero = live) or None -> [B, Lq, nh * dh]."""
     B, Lq, D = q.shape
     Lk = k.size(1)
-    qh, kh, vh = q.view(B, Lq, num_heads, -1), k.view(B, Lk, num_heads, -1), v.view(B, Lk, num_heads, -1)
+    dh = D // num_heads                          # (spelled out: -1 cannot be inferred for an empty batch or query set)
+    qh, kh, vh = q.view(B, Lq, num_heads, dh), k.view(B, Lk, num_heads, dh), v.view(B, Lk, num_heads, dh)
     s = th.einsum("bind,bjnd->bijn", qh, kh) * scale
     if kmask is not None:
         s = s.masked_fill(_as_mask(kmask, B, Lk).view(B, 1, Lk, 1) == 0, _INF)
@@ -69,6 +70,13 @@ def _u8(m, B, L):
     return (m != 0).contiguous().view(th.uint8)
 
 
+def _aligned(t):
+    """``t`` as the kernels read it (row-major, float4 loads): itself where it is contiguous and 16-byte aligned, else a
+    copy (a contiguous view at an odd offset into a larger buffer is contiguous and not aligned)."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class SparsemaxAttention(th.autograd.Function):
     """The HIP kernels (csrc/dmp_attn.hip) as one autograd node: forward ``dmp_attn_fwd``, backward ``dmp_attn_bwd``
     (scores recomputed from Q and K).  No host round trip: workspaces follow from the shapes alone."""
@@ -80,7 +88,7 @@ class SparsemaxAttention(th.autograd.Function):
         B, Lq, D = q.shape
         Lk = k.size(1)
         dh = D // num_heads
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        q, k, v = _aligned(q), _aligned(k), _aligned(v)
         _lib.require_gpu(q, k, v)
         qm, km = _u8(qmask, B, Lq), _u8(kmask, B, Lk)
         o = _out(q.shape, th.float32, q.device)
@@ -101,7 +109,7 @@ class SparsemaxAttention(th.autograd.Function):
         qm, km = ctx.masks
         B, Lq, D = q.shape
         Lk = k.size(1)
-        do = do.contiguous()
+        do = _aligned(do)
         delta = _out((B, Lq, ctx.num_heads), th.float32, q.device)
         dq, dk, dv = _out(q.shape, th.float32, q.device), _out(k.shape, th.float32, q.device), _out(v.shape, th.float32, q.device)
         _lib.check(lib.dmp_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _lib.ptr(qm), _lib.ptr(km), do.data_ptr(), tau.data_ptr(),

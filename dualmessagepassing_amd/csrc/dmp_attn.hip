@@ -557,17 +557,18 @@ int dmp_attn_bwd(const float *Q, const float *K, const float *V, const uint8_t *
   AttnArgs a{Q, K, V, qmask, kmask, B, Lq, Lk, nh, scale};
   if (!dh_ok(dh)) return DMP_ERR_UNSUPPORTED;
   if (B == 0 || Lk == 0) return DMP_OK;
-  if (!args_ok(a, dh) || !dO || !tau || !supp || !delta || !dQ || !dK || !dV) return DMP_ERR_BAD_ARG;
-  if (!aligned16(dO) || !aligned16(dQ) || !aligned16(dK) || !aligned16(dV)) return DMP_ERR_BAD_ARG;
-  if (row_tiles(Lq, 2) * nh * B >= (int64_t)1 << 31 || (Lk + 63) * nh * B >= (int64_t)1 << 31) return DMP_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (Lq == 0) {   // no rows: the key gradients are zero
+  if (Lq == 0) {   // no rows (the per-row arrays are empty and may be NULL): the key gradients are zero
+    if (B < 0 || Lk < 0 || nh < 1 || !dK || !dV) return DMP_ERR_BAD_ARG;
     const size_t n = (size_t)(B * Lk * nh * dh) * sizeof(float);
     hipError_t e = hipMemsetAsync(dK, 0, n, st);
     if (e == hipSuccess) e = hipMemsetAsync(dV, 0, n, st);
     if (e != hipSuccess) { set_last_hip_error(e); return DMP_ERR_HIP; }
     return DMP_OK;
   }
+  if (!args_ok(a, dh) || !dO || !tau || !supp || !delta || !dQ || !dK || !dV) return DMP_ERR_BAD_ARG;
+  if (!aligned16(dO) || !aligned16(dQ) || !aligned16(dK) || !aligned16(dV)) return DMP_ERR_BAD_ARG;
+  if (row_tiles(Lq, 2) * nh * B >= (int64_t)1 << 31 || (Lk + 63) * nh * B >= (int64_t)1 << 31) return DMP_ERR_UNSUPPORTED;
   switch (dh) {
     case 4: return bwd_dh<4>(a, dO, tau, supp, delta, dQ, dK, dV, st);
     case 8: return bwd_dh<8>(a, dO, tau, supp, delta, dQ, dK, dV, st);

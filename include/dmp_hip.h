@@ -1539,6 +1539,8 @@ int dmp_gemm_k64(const float *A, int64_t lda, const float *B, int64_t ldb, int b
  * 0 = every key masked).  No [B, Lq, Lk, nh] tensor; workspaces depend on the shapes only (graph capture safe).
  * Backward: dO -> dQ, dK, dV; delta [B, Lq, nh] fp32 is scratch (mean over the support of dO_i . V_j).
  * No float atomics: bitwise reproducible.
+ * B == 0 or Lq == 0: nothing is launched and the per-row pointers (Q, O, tau, supp, dO, delta, dQ) may be NULL; the
+ * backward at Lq == 0 writes zeros to dK and dV.
  */
 int dmp_attn_supported_dh(int dh);
 int dmp_attn_fwd(const float *Q, const float *K, const float *V, const uint8_t *qmask, const uint8_t *kmask, int64_t B, int64_t Lq,

@@ -137,15 +137,17 @@ def test_every_output_is_written(gpu, monkeypatch):
 
 
 def test_dispatch_kernel_or_tensor_path(gpu, monkeypatch):
-    """Head widths in KERNEL_DH take the kernels; other widths and non-fp32 inputs take the tensor-op path."""
+    """Head widths in KERNEL_DH take the kernels, also from contiguous views that start 4 bytes into a larger buffer (the
+    kernels load float4: SparsemaxAttention copies those); other widths and non-fp32 inputs take the tensor-op path."""
     from dualmessagepassing_amd import attn
     calls = []
     orig = attn.attention_tensor
     monkeypatch.setattr(attn, "attention_tensor", lambda *a: (calls.append(1), orig(*a))[1])
-    for dh, dtype, want_kernel in ((16, th.float32, True), (4, th.float32, True), (12, th.float32, False), (2, th.float32, False),
-                                   (16, th.float64, False)):
-        q = th.randn(2, 5, 4 * dh, device=gpu, dtype=dtype)
-        k = th.randn(2, 6, 4 * dh, device=gpu, dtype=dtype)
+    for dh, dtype, want_kernel, offset in ((16, th.float32, True, 0), (4, th.float32, True, 0), (12, th.float32, False, 0),
+                                           (2, th.float32, False, 0), (16, th.float64, False, 0), (16, th.float32, True, 1)):
+        q = th.randn(2 * 5 * 4 * dh + offset, device=gpu, dtype=dtype)[offset:].view(2, 5, 4 * dh)
+        k = th.randn(2 * 6 * 4 * dh + offset, device=gpu, dtype=dtype)[offset:].view(2, 6, 4 * dh)
+        assert q.data_ptr() % 16 == 4 * offset and k.data_ptr() % 16 == 4 * offset and q.is_contiguous() and k.is_contiguous()
         assert attn.kernel_ok(q, k, k, 4) == want_kernel
         n = len(calls)
         out = attn.sparsemax_attention(q, k, k, None, None, 4, 0.5)
