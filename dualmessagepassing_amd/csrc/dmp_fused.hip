@@ -1021,7 +1021,9 @@ static int adamw_launch(float *param, const float *grad, float *exp_avg, float *
   }
   a.nskip = nskip;
   for (int s = 0; s < nskip; ++s) {
-    if (skip_lo[s] % 4 || skip_hi[s] % 4 || skip_lo[s] > skip_hi[s]) return DMP_ERR_BAD_ARG;
+    // (a range may end at n itself when n is no multiple of 4: the kernel tests the first element of a group of 4 against
+    // the range, so the last, partial group is left alone with it)
+    if (skip_lo[s] % 4 || (skip_hi[s] % 4 && skip_hi[s] != n) || skip_lo[s] > skip_hi[s]) return DMP_ERR_BAD_ARG;
     a.skip_lo[s] = skip_lo[s]; a.skip_hi[s] = skip_hi[s];
   }
   int64_t nb = (n / 4 + kBlock) / kBlock;

@@ -270,7 +270,8 @@ class FlatAdamW(torch.optim.Optimizer):
     On the flat parameter of ``FlatGradSync.flatten_parameters()`` every parameter TENSOR of the buffer keeps its own step
     count (``dmp_adamw_step_segments``: a tensor that first receives a gradient at step k starts its bias corrections at
     1, one without a gradient is left alone -- ``torch.optim.AdamW``'s per-tensor state); the counts and the learning rate
-    live in device memory, so such a step also replays from a HIP graph.
+    live in device memory, so such a step also replays from a HIP graph.  ``eps = 0`` is refused on such a buffer (its
+    padding floats would compute 0 / 0).
 
     ``capturable=True``: the step count and the learning rate live in device memory (``dmp_adamw_step_dev``), so a step
     recorded in a HIP graph (``StepGraph``) replays correctly; outside a capture ``step()`` writes the group's current
@@ -377,6 +378,11 @@ class FlatAdamW(torch.optim.Optimizer):
                 _lib.require_gpu(p, p.grad)
                 if p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
                     raise ValueError("FlatAdamW needs contiguous fp32 parameters and gradients")
+                if group["eps"] == 0 and getattr(p, "_dmp_seg", None) is not None:
+                    # the padding floats between the tensors of a flat buffer have m = v = 0 for ever: 0 / (0 + eps) keeps them
+                    # zero, 0 / 0 would put NaN into the parameter buffer where the per-tensor optimizer has no such element
+                    raise ValueError("FlatAdamW: eps = 0 on the flat buffer of FlatGradSync.flatten_parameters() "
+                                     "(its padding floats would become NaN)")
                 st = self.state[p]
                 if not st:
                     st["step"] = 0
@@ -421,15 +427,17 @@ class FlatAdamW(torch.optim.Optimizer):
                         self.sync_hyper()
                 # runs of the buffer whose parameters received a gradient (FlatGradSync.pack); parameters without one
                 # are left untouched like torch.optim.AdamW does (they share the buffer's step count, though)
-                runs = getattr(p, "_dmp_live_runs", None) or [(0, p.numel())]
+                runs = getattr(p, "_dmp_live_runs", None)    # (None: all of it; an EMPTY list: no tensor has a gradient)
+                if runs is None:
+                    runs = [(0, p.numel())]
                 mx = st.get("max_exp_avg_sq")
                 gaps, pos = [], 0                            # the complement of the live runs: what the launch leaves alone
                 for off, n in runs:
                     if off > pos:
                         gaps.append((pos, off))
                     pos = off + n
-                if pos < p.numel():
-                    gaps.append((pos, p.numel() // 4 * 4))
+                if pos < p.numel():                          # (to the very end: the kernel leaves a last partial group of 4 alone too)
+                    gaps.append((pos, p.numel()))
                 if len(gaps) <= _abi.DMP_ADAMW_MAX_SKIP:     # one launch
                     import ctypes
                     lo = (ctypes.c_int64 * max(len(gaps), 1))(*[g[0] for g in gaps])

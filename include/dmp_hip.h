@@ -833,8 +833,8 @@ int dmp_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_a
                    float *max_exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, int64_t step, void *stream);
 /* The same step, leaving the ranges [skip_lo[k], skip_hi[k]) of the buffer untouched (nskip <= DMP_ADAMW_MAX_SKIP host
- * entries, multiples of 4 floats): the slices of parameters that received no gradient this step, which
- * torch.optim.AdamW skips (no decay, no moment update). */
+ * entries, multiples of 4 floats; a range that ends the buffer may end at n itself, whatever n is): the slices of
+ * parameters that received no gradient this step, which torch.optim.AdamW skips (no decay, no moment update). */
 #define DMP_ADAMW_MAX_SKIP 16
 int dmp_adamw_step_skip(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
                         float *max_exp_avg_sq, int64_t n, double lr, double beta1, double beta2, double eps,
