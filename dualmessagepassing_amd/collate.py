@@ -13,18 +13,12 @@ from ._lib import check, ptr, stream_ptr
 from .graph import BatchedGraph
 
 
-def collate_device(local_src, local_dst, num_nodes, num_edges, total_nodes, total_edges, ndata=None,
-                   edata=None, with_segments=True, max_nodes=None, max_edges=None):
-    """Device collate of per-graph LOCAL edge lists laid out back to back.
-
-    local_src/local_dst [E] int64 (device), num_nodes/num_edges [B] int64 (device);
-    total_nodes/total_edges are host ints (the dataset knows them; no device sync here).
-    max_nodes/max_edges (optional host ints): the largest graph of the batch, which the dataset also
-    knows -- the model's padding helpers then need no ``sizes.max().item()`` round trip per batch.
-    Returns a BatchedGraph with global endpoints, ``batch_num_nodes/edges`` and, if
-    ``with_segments``, ``node_graph`` / ``edge_graph`` (owning graph per node / edge).
-    """
-    lib = _lib.load()
+def _collate_job(local_src, local_dst, num_nodes, num_edges, total_nodes, total_edges, ndata=None, edata=None,
+                 with_segments=True, max_nodes=None, max_edges=None):
+    """One batch's share of a collate: the checks and the output tensors.  Returns ``(job, finish)``: the pointers and sizes
+    of the batch in the order ``dmp_collate`` takes them, which is the order of ``dmp_collate_job``'s fields, and the
+    function that makes the BatchedGraph once a launch has written the outputs (it also keeps the contiguous inputs alive
+    until then)."""
     _lib.require_gpu(local_src, local_dst, num_nodes, num_edges)
     for t in (local_src, local_dst, num_nodes, num_edges):
         if t.dtype != torch.int64:
@@ -41,18 +35,39 @@ def collate_device(local_src, local_dst, num_nodes, num_edges, total_nodes, tota
     dst = torch.empty(E, dtype=torch.int64, device=dev)
     eg = torch.empty(E, dtype=torch.int32, device=dev) if with_segments else None
     ng = torch.empty(N, dtype=torch.int32, device=dev) if with_segments else None
-    check(lib.dmp_collate(ptr(local_src), ptr(local_dst), ptr(num_nodes), ptr(num_edges), B, N, E,
-                          ptr(node_off), ptr(edge_off), ptr(src), ptr(dst), ptr(eg), ptr(ng), stream_ptr()),
-          "dmp_collate")
-    g = BatchedGraph(src, dst, N, num_nodes, num_edges, ndata, edata)
-    g.node_graph, g.edge_graph = ng, eg
-    g.node_offsets, g.edge_offsets = node_off, edge_off
-    g.max_num_nodes = None if max_nodes is None else int(max_nodes)
-    g.max_num_edges = None if max_edges is None else int(max_edges)
-    from . import ops
-    g.tiling = ops.graph_tiling(node_off, edge_off, B, g.max_num_edges)
-    g.node_tiling = ops.graph_node_tiling(node_off, edge_off, B, g.max_num_nodes)
-    return g
+    job = (ptr(local_src), ptr(local_dst), ptr(num_nodes), ptr(num_edges), B, N, E,
+           ptr(node_off), ptr(edge_off), ptr(src), ptr(dst), ptr(eg), ptr(ng))
+
+    def finish(inputs=(local_src, local_dst)):                  # (inputs: held, not used -- the launch reads them)
+        from . import ops
+        g = BatchedGraph(src, dst, N, num_nodes, num_edges, ndata, edata)
+        g.node_graph, g.edge_graph = ng, eg
+        g.node_offsets, g.edge_offsets = node_off, edge_off
+        g.max_num_nodes = None if max_nodes is None else int(max_nodes)
+        g.max_num_edges = None if max_edges is None else int(max_edges)
+        g.tiling = ops.graph_tiling(node_off, edge_off, B, g.max_num_edges)
+        g.node_tiling = ops.graph_node_tiling(node_off, edge_off, B, g.max_num_nodes)
+        return g
+
+    return job, finish
+
+
+def collate_device(local_src, local_dst, num_nodes, num_edges, total_nodes, total_edges, ndata=None,
+                   edata=None, with_segments=True, max_nodes=None, max_edges=None):
+    """Device collate of per-graph LOCAL edge lists laid out back to back.
+
+    local_src/local_dst [E] int64 (device), num_nodes/num_edges [B] int64 (device);
+    total_nodes/total_edges are host ints (the dataset knows them; no device sync here).
+    max_nodes/max_edges (optional host ints): the largest graph of the batch, which the dataset also
+    knows -- the model's padding helpers then need no ``sizes.max().item()`` round trip per batch.
+    Returns a BatchedGraph with global endpoints, ``batch_num_nodes/edges`` and, if
+    ``with_segments``, ``node_graph`` / ``edge_graph`` (owning graph per node / edge).
+    """
+    lib = _lib.load()
+    job, finish = _collate_job(local_src, local_dst, num_nodes, num_edges, total_nodes, total_edges, ndata, edata,
+                               with_segments, max_nodes, max_edges)
+    check(lib.dmp_collate(*job, stream_ptr()), "dmp_collate")
+    return finish()
 
 
 def collate_device_many(batches):
@@ -61,45 +76,14 @@ def collate_device_many(batches):
     ``num_nodes``, ``num_edges``, ``total_nodes``, ``total_edges`` and optionally ``ndata``, ``edata``, ``max_nodes``,
     ``max_edges``).  Returns the BatchedGraphs in order."""
     lib = _lib.load()
-    if not 0 < len(batches) <= _abi.DMP_COLLATE_MAX_JOBS or any(int(b["num_nodes"].numel()) == 0 or int(b["num_nodes"].numel()) > 2048 for b in batches):
-        return [collate_device(b["local_src"], b["local_dst"], b["num_nodes"], b["num_edges"], b["total_nodes"], b["total_edges"],
-                               b.get("ndata"), b.get("edata"), True, b.get("max_nodes"), b.get("max_edges")) for b in batches]
-    J = (_abi.dmp_collate_job * len(batches))()
-    made, keep = [], []
-    for k, b in enumerate(batches):
-        ls, ld, nn, ne = b["local_src"], b["local_dst"], b["num_nodes"], b["num_edges"]
-        _lib.require_gpu(ls, ld, nn, ne)
-        for t in (ls, ld, nn, ne):
-            if t.dtype != torch.int64:
-                raise _lib.DmpError("collate inputs must be int64")
-        ls, ld, nn, ne = ls.contiguous(), ld.contiguous(), nn.contiguous(), ne.contiguous()
-        B, N, E = int(nn.numel()), int(b["total_nodes"]), int(b["total_edges"])
-        if ls.numel() != E or ld.numel() != E or ne.numel() != B:
-            raise _lib.DmpError("collate: inconsistent sizes")
-        dev = ls.device
-        offs = torch.empty(2 * (B + 1), dtype=torch.int64, device=dev)
-        ends = torch.empty((2, E), dtype=torch.int64, device=dev)
-        eg = torch.empty(E, dtype=torch.int32, device=dev)
-        ng = torch.empty(N, dtype=torch.int32, device=dev)
-        j = J[k]
-        j.local_src, j.local_dst, j.num_nodes, j.num_edges, j.B, j.N, j.E = ptr(ls), ptr(ld), ptr(nn), ptr(ne), B, N, E
-        j.node_off, j.edge_off, j.src, j.dst = ptr(offs[:B + 1]), ptr(offs[B + 1:]), ptr(ends[0]), ptr(ends[1])
-        j.edge_graph, j.node_graph = ptr(eg), ptr(ng)
-        keep.append((ls, ld, nn, ne))
-        made.append((b, nn, ne, N, B, offs, ends, eg, ng))
-    check(lib.dmp_collate_jobs(J, len(batches), stream_ptr()), "dmp_collate_jobs")
-    from . import ops
-    out = []
-    for b, nn, ne, N, B, offs, ends, eg, ng in made:
-        g = BatchedGraph(ends[0], ends[1], N, nn, ne, b.get("ndata"), b.get("edata"))
-        g.node_graph, g.edge_graph = ng, eg
-        g.node_offsets, g.edge_offsets = offs[:B + 1], offs[B + 1:]
-        g.max_num_nodes = None if b.get("max_nodes") is None else int(b["max_nodes"])
-        g.max_num_edges = None if b.get("max_edges") is None else int(b["max_edges"])
-        g.tiling = ops.graph_tiling(g.node_offsets, g.edge_offsets, B, g.max_num_edges)
-        g.node_tiling = ops.graph_node_tiling(g.node_offsets, g.edge_offsets, B, g.max_num_nodes)
-        out.append(g)
-    return out
+    args = [(b["local_src"], b["local_dst"], b["num_nodes"], b["num_edges"], b["total_nodes"], b["total_edges"],
+             b.get("ndata"), b.get("edata"), True, b.get("max_nodes"), b.get("max_edges")) for b in batches]
+    if not 0 < len(batches) <= _abi.DMP_COLLATE_MAX_JOBS or any(not 0 < int(b["num_nodes"].numel()) <= 2048 for b in batches):
+        return [collate_device(*a) for a in args]
+    made = [_collate_job(*a) for a in args]
+    J = (_abi.dmp_collate_job * len(made))(*[_abi.dmp_collate_job(*job) for job, _ in made])
+    check(lib.dmp_collate_jobs(J, len(made), stream_ptr()), "dmp_collate_jobs")
+    return [finish() for _, finish in made]
 
 
 def batch(graphs, device=None):

@@ -1,13 +1,21 @@
 // Integer graph-index kernels of the dual-message-passing hot path (gfx950).
 //
-//   csr_build          counting sort of the edge list by dst (or src); rows in
-//                      ascending eid -> every later segment sum has one fixed order
+//   scans              three-phase exclusive prefix sum; its two pieces also serve the CSR build and the collate
+//   csr_build(_pair)   counting sort of the edge list by dst and / or src (one kernel family, a key per blockIdx.y);
+//                      rows in ascending eid -> every later segment sum has one fixed order
+//   csr_build_graphs   both CSRs of a block-diagonal batch in one launch, a workgroup per graph
 //   incidence_build    in-edges and out-edges (flag flipped) per node, merged by edge id
 //   degree_coef        2(1+log2(1+out_deg))
-//   collate            dgl.batch: node-offset concatenation
+//   collate(_jobs)     dgl.batch: node-offset concatenation, several batches per launch
 //   add_reversed_edges train.py:299-327
-//   line_graph_*       utils/graph.py:74-169 (directed line graph, emission order)
-//   scans              exclusive prefix sums (int32 / int64)
+//   line_graph_*       utils/graph.py:74-169 (directed line graph, emission order); first edge of an id
+//   dedupe_first       first item of every (a, l, b) key, by an open-addressing table
+//   subiso_* / dual_*  subisomorphism weights of a batch; the graph edge every pattern key lands on
+//   random_walks, sample_in_edges   UNC's mini-batch samplers on a counter-based generator
+//   pool_index_jobs    chunked row ranges of the pooled heads; pool_weight_sums
+//   csr_keep, incidence_keep        the in-CSR / incidence CSR over the edges a 0 / 1 gate keeps
+//   class_tiles(_gated)             degree-class tile list of the typed edge kernels
+//   concat_pairs, table_rows, len_masks, scalar_filter_gates   small per-batch jobs, several per launch
 //
 // Every result here is an integer array and must equal the reference's bit for
 // bit; nothing depends on atomic arrival order (rows are sorted after the
@@ -47,11 +55,12 @@ __device__ __forceinline__ T block_exclusive_scan(T v, T *lds, T &total) {
   return wave_off + inc - v;
 }
 
+// (A) for one tile: load kScanItems items per thread, scan them over the workgroup, write the exclusive prefixes inside the
+// tile; returns the tile's total (the same in every thread).  Every thread of the workgroup calls it.
 template <typename TI, typename TO>
-__global__ __launch_bounds__(kBlock) void scan_tiles(const TI *__restrict__ in, int64_t n,
-                                                     TO *__restrict__ out, TO *__restrict__ tile_sum) {
+__device__ __forceinline__ TO scan_one_tile(const TI *__restrict__ in, int64_t n, int64_t tile, TO *__restrict__ out) {
   __shared__ TO lds[kBlock / kWave];
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+  const int64_t base = tile * kScanTile + (int64_t)threadIdx.x * kScanItems;
   TO v[kScanItems];
   TO s = 0;
 #pragma unroll
@@ -66,12 +75,11 @@ __global__ __launch_bounds__(kBlock) void scan_tiles(const TI *__restrict__ in, 
     if (base + k < n) out[base + k] = pre;
     pre += v[k];
   }
-  if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+  return total;
 }
-
+// (B) one workgroup: the tile totals become the tiles' offsets, kBlock at a time with a carry; returns the grand total.
 template <typename TO>
-__global__ __launch_bounds__(kBlock) void scan_tile_sums(TO *__restrict__ tile_sum, int64_t ntiles,
-                                                         TO *__restrict__ grand_total) {
+__device__ __forceinline__ TO scan_tile_totals(TO *__restrict__ tile_sum, int64_t ntiles) {
   __shared__ TO lds[kBlock / kWave];
   TO carry = 0;
   for (int64_t base = 0; base < ntiles; base += kBlock) {
@@ -82,7 +90,21 @@ __global__ __launch_bounds__(kBlock) void scan_tile_sums(TO *__restrict__ tile_s
     if (i < ntiles) tile_sum[i] = carry + pre;
     carry += total;
   }
-  if (threadIdx.x == 0) *grand_total = carry;
+  return carry;
+}
+
+template <typename TI, typename TO>
+__global__ __launch_bounds__(kBlock) void scan_tiles(const TI *__restrict__ in, int64_t n,
+                                                     TO *__restrict__ out, TO *__restrict__ tile_sum) {
+  const TO total = scan_one_tile<TI, TO>(in, n, blockIdx.x, out);
+  if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+template <typename TO>
+__global__ __launch_bounds__(kBlock) void scan_tile_sums(TO *__restrict__ tile_sum, int64_t ntiles,
+                                                         TO *__restrict__ grand_total) {
+  const TO total = scan_tile_totals<TO>(tile_sum, ntiles);
+  if (threadIdx.x == 0) *grand_total = total;
 }
 
 template <typename TO>
@@ -111,31 +133,6 @@ int exclusive_scan(const TI *in, int64_t n, TO *out, TO *tile_ws, hipStream_t st
 }
 
 // ------------------------------------------------------------------ CSR build
-__global__ __launch_bounds__(kBlock) void csr_count(const int64_t *__restrict__ key, int64_t E,
-                                                    int64_t N, int32_t *__restrict__ cnt,
-                                                    int32_t *__restrict__ key32,
-                                                    int32_t *__restrict__ status) {
-  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (e >= E) return;
-  const int64_t k = key[e];
-  const bool ok = k >= 0 && k < N;
-  if (key32) key32[e] = ok ? (int32_t)k : 0;
-  if (ok) atomicAdd(&cnt[k], 1);
-  else atomicOr(status, 1);
-}
-
-__global__ __launch_bounds__(kBlock) void csr_fill(const int64_t *__restrict__ key,
-                                                   const uint8_t *__restrict__ flag, int64_t E,
-                                                   int64_t N, int32_t *__restrict__ cursor,
-                                                   int32_t *__restrict__ ent) {
-  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (e >= E) return;
-  const int64_t k = key[e];
-  if (k < 0 || k >= N) return;
-  const int pos = atomicAdd(&cursor[k], 1);
-  ent[pos] = ((int32_t)e << 1) | (flag ? (flag[e] ? 1 : 0) : 0);
-}
-
 // Restore ascending eid inside each row (the atomic fill arrives almost sorted,
 // so insertion sort is near linear); rows longer than kHeapFrom use heap sort.
 constexpr int kHeapFrom = 96;
@@ -200,21 +197,16 @@ __device__ __forceinline__ void csr_sort_row(const int32_t *__restrict__ rowptr,
   csr_sort_span(ent + beg, end - beg);
 }
 
-__global__ __launch_bounds__(kBlock) void csr_sort_rows(const int32_t *__restrict__ rowptr, int64_t N,
-                                                        int32_t *__restrict__ ent,
-                                                        int64_t *__restrict__ degree) {
-  csr_sort_row(rowptr, N, ent, degree, (int64_t)blockIdx.x * kBlock + threadIdx.x);
-}
-
-// ---- both CSRs of a graph (by destination and by source) built side by side: blockIdx.y picks the key array, so the
-// nine dispatches of a build are paid once for the pair
-struct CsrPair {
+// ---- the CSR build: count the keys per node, scan the counts into row offsets (the three scan phases; the last one also
+// turns the counters into the fill cursors), fill through the cursors, sort every row.  blockIdx.y picks the key array: slot 0
+// alone is dmp_csr_build, slots 0 and 1 (by destination and by source) are dmp_csr_build_pair at the same six dispatches.
+struct CsrSlots {
   const int64_t *key[2];
   int32_t *rowptr[2], *ent[2], *key32[2], *cnt[2], *tiles[2];
   int64_t *degree[2];
-  int32_t *status;                                              // [2]
+  int32_t *status;                                              // a word per slot
 };
-__global__ __launch_bounds__(kBlock) void csr_count_pair(const CsrPair p, int64_t E, int64_t N) {
+__global__ __launch_bounds__(kBlock) void csr_count_k(const CsrSlots p, int64_t E, int64_t N) {
   const int y = blockIdx.y;
   const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (e >= E) return;
@@ -224,45 +216,18 @@ __global__ __launch_bounds__(kBlock) void csr_count_pair(const CsrPair p, int64_
   if (ok) atomicAdd(&p.cnt[y][k], 1);
   else atomicOr(p.status + y, 1);
 }
-__global__ __launch_bounds__(kBlock) void scan_tiles_pair(const CsrPair p, int64_t n) {
-  __shared__ int32_t lds[kBlock / kWave];
+__global__ __launch_bounds__(kBlock) void csr_scan_tiles_k(const CsrSlots p, int64_t n) {
   const int y = blockIdx.y;
-  const int32_t *__restrict__ in = p.cnt[y];
-  int32_t *__restrict__ out = p.rowptr[y];
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-  int32_t v[kScanItems];
-  int32_t sum = 0;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    v[k] = (base + k < n) ? in[base + k] : 0;
-    sum += v[k];
-  }
-  int32_t total;
-  int32_t pre = block_exclusive_scan<int32_t>(sum, lds, total);
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    if (base + k < n) out[base + k] = pre;
-    pre += v[k];
-  }
+  const int32_t total = scan_one_tile<int32_t, int32_t>(p.cnt[y], n, blockIdx.x, p.rowptr[y]);
   if (threadIdx.x == 0) p.tiles[y][blockIdx.x] = total;
 }
-__global__ __launch_bounds__(kBlock) void scan_tile_sums_pair(const CsrPair p, int64_t ntiles, int64_t n) {
-  __shared__ int32_t lds[kBlock / kWave];
+__global__ __launch_bounds__(kBlock) void csr_scan_totals_k(const CsrSlots p, int64_t ntiles, int64_t n) {
   const int y = blockIdx.y;
-  int32_t *__restrict__ tile_sum = p.tiles[y];
-  int32_t carry = 0;
-  for (int64_t base = 0; base < ntiles; base += kBlock) {
-    const int64_t i = base + threadIdx.x;
-    const int32_t v = i < ntiles ? tile_sum[i] : 0;
-    int32_t total;
-    const int32_t pre = block_exclusive_scan<int32_t>(v, lds, total);
-    if (i < ntiles) tile_sum[i] = carry + pre;
-    carry += total;
-  }
-  if (threadIdx.x == 0) p.rowptr[y][n] = carry;
+  const int32_t total = scan_tile_totals<int32_t>(p.tiles[y], ntiles);
+  if (threadIdx.x == 0) p.rowptr[y][n] = total;
 }
 // rowptr += tile offset; the counters become the fill cursors (= rowptr)
-__global__ __launch_bounds__(kBlock) void scan_finish_pair(const CsrPair p, int64_t n) {
+__global__ __launch_bounds__(kBlock) void csr_scan_finish_k(const CsrSlots p, int64_t n) {
   const int y = blockIdx.y;
   const int32_t off = p.tiles[y][blockIdx.x];
   const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
@@ -274,7 +239,7 @@ __global__ __launch_bounds__(kBlock) void scan_finish_pair(const CsrPair p, int6
       p.cnt[y][base + k] = v;
     }
 }
-__global__ __launch_bounds__(kBlock) void csr_fill_pair(const CsrPair p, const uint8_t *__restrict__ flag, int64_t E, int64_t N) {
+__global__ __launch_bounds__(kBlock) void csr_fill_k(const CsrSlots p, const uint8_t *__restrict__ flag, int64_t E, int64_t N) {
   const int y = blockIdx.y;
   const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (e >= E) return;
@@ -283,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void csr_fill_pair(const CsrPair p, const u
   const int pos = atomicAdd(&p.cnt[y][k], 1);
   p.ent[y][pos] = ((int32_t)e << 1) | (flag ? (flag[e] ? 1 : 0) : 0);
 }
-__global__ __launch_bounds__(kBlock) void csr_sort_rows_pair(const CsrPair p, int64_t N) {
+__global__ __launch_bounds__(kBlock) void csr_sort_rows_k(const CsrSlots p, int64_t N) {
   const int y = blockIdx.y;
   csr_sort_row(p.rowptr[y], N, p.ent[y], p.degree[y], (int64_t)blockIdx.x * kBlock + threadIdx.x);
 }
@@ -351,12 +316,6 @@ __global__ __launch_bounds__(kBlock) void csr_graphs_k(const CsrGraphs p) {
   }
 }
 
-__global__ __launch_bounds__(kBlock) void copy_i32(const int32_t *__restrict__ a, int64_t n,
-                                                   int32_t *__restrict__ b) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i < n) b[i] = a[i];
-}
-
 // ------------------------------------------------------------------ incidence
 __global__ __launch_bounds__(kBlock) void incidence_ptr(const int32_t *__restrict__ in_ptr,
                                                         const int32_t *__restrict__ out_ptr, int64_t N,
@@ -410,71 +369,13 @@ __device__ __forceinline__ int64_t upper_graph(const int64_t *off, int64_t B, in
   }
   return lo;
 }
-// node and edge offsets in one launch (blockIdx.y: 0 = nodes, 1 = edges; B <= one scan tile), then the edge and the
-// node pass in one launch: four dispatches of a collate become two
-__global__ __launch_bounds__(kBlock) void collate_offsets(const int64_t *__restrict__ num_nodes, const int64_t *__restrict__ num_edges,
-                                                          int64_t B, int64_t *__restrict__ node_off, int64_t *__restrict__ edge_off) {
-  __shared__ int64_t lds[kBlock / kWave];
-  const int64_t *__restrict__ in = blockIdx.y == 0 ? num_nodes : num_edges;
-  int64_t *__restrict__ out = blockIdx.y == 0 ? node_off : edge_off;
-  const int64_t base = (int64_t)threadIdx.x * kScanItems;
-  int64_t v[kScanItems];
-  int64_t sum = 0;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    v[k] = (base + k < B) ? in[base + k] : 0;
-    sum += v[k];
-  }
-  int64_t total;
-  int64_t pre = block_exclusive_scan<int64_t>(sum, lds, total);
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    if (base + k < B) out[base + k] = pre;
-    pre += v[k];
-  }
-  if (threadIdx.x == 0) out[B] = total;
-}
-__global__ __launch_bounds__(kBlock) void collate_both(const int64_t *__restrict__ ls, const int64_t *__restrict__ ld,
-                                                       const int64_t *__restrict__ node_off, const int64_t *__restrict__ edge_off,
-                                                       int64_t B, int64_t E, int64_t N, int64_t *__restrict__ src,
-                                                       int64_t *__restrict__ dst, int32_t *__restrict__ edge_graph,
-                                                       int32_t *__restrict__ node_graph) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (blockIdx.y == 0) {
-    if (i >= E) return;
-    const int64_t g = upper_graph(edge_off, B, i);
-    const int64_t o = node_off[g];
-    src[i] = ls[i] + o;
-    dst[i] = ld[i] + o;
-    if (edge_graph) edge_graph[i] = (int32_t)g;
-  } else {
-    if (i >= N || !node_graph) return;
-    node_graph[i] = (int32_t)upper_graph(node_off, B, i);
-  }
-}
-
-// several batches (the pattern batch and the target batch of a step) in the same two launches: blockIdx.y = 2 job + part
+// One or several batches (the pattern batch and the target batch of a step) in two launches, blockIdx.y = 2 job + part:
+// the node (part 0) and the edge (part 1) offsets of every job (B <= one scan tile), then every job's edge and node pass.
 struct CollateJobs { dmp_collate_job job[DMP_COLLATE_MAX_JOBS]; };
 __global__ __launch_bounds__(kBlock) void collate_offsets_jobs(const CollateJobs t) {
-  __shared__ int64_t lds[kBlock / kWave];
   const dmp_collate_job &j = t.job[blockIdx.y >> 1];
-  const int64_t *__restrict__ in = (blockIdx.y & 1) == 0 ? j.num_nodes : j.num_edges;
   int64_t *__restrict__ out = (blockIdx.y & 1) == 0 ? j.node_off : j.edge_off;
-  const int64_t base = (int64_t)threadIdx.x * kScanItems;
-  int64_t v[kScanItems];
-  int64_t sum = 0;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    v[k] = (base + k < j.B) ? in[base + k] : 0;
-    sum += v[k];
-  }
-  int64_t total;
-  int64_t pre = block_exclusive_scan<int64_t>(sum, lds, total);
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    if (base + k < j.B) out[base + k] = pre;
-    pre += v[k];
-  }
+  const int64_t total = scan_one_tile<int64_t, int64_t>((blockIdx.y & 1) == 0 ? j.num_nodes : j.num_edges, j.B, 0, out);
   if (threadIdx.x == 0) out[j.B] = total;
 }
 __global__ __launch_bounds__(kBlock) void collate_both_jobs(const CollateJobs t) {
@@ -1016,45 +917,59 @@ __global__ __launch_bounds__(kBlock) void ct_live_k(const int32_t *__restrict__ 
 // ---- the in-CSR of the edges a 0 / 1 gate keeps (dmp_csr_keep): (1) every node counts the kept entries of its row, every
 // block adds its nodes' counts up; (2) every block sums the block totals before it, ranks its nodes with a block scan, and
 // every node copies the kept entries of its row in order.  No atomics: the layout is a function of the inputs alone.
-__global__ __launch_bounds__(kBlock) void keep_count_k(const int32_t *__restrict__ in_ptr, const int32_t *__restrict__ in_ent,
-                                                       const float *__restrict__ gate, int64_t N, int32_t *__restrict__ row_cnt,
-                                                       int32_t *__restrict__ blk) {
+//
+// The block bookkeeping of the two passes, shared by the three kernel pairs below.  Each holds a barrier: every thread of the
+// block calls it.
+__device__ __forceinline__ void block_total_to(int c, int32_t *__restrict__ blk) {      // blk[blockIdx.x] = the block's sum of c
   __shared__ int red[kBlock / 64];
-  const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  int c = 0;
-  if (v < N) {
-    for (int q = in_ptr[v], hi = in_ptr[v + 1]; q < hi; ++q) c += gate[in_ent[q] >> 1] != 0.f;
-    row_cnt[v] = c;
-  }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) { int t = 0; for (int i = 0; i < kBlock / 64; ++i) t += red[i]; blk[blockIdx.x] = t; }
 }
-__global__ __launch_bounds__(kBlock) void keep_fill_k(const int32_t *__restrict__ in_ptr, const int32_t *__restrict__ in_ent,
-                                                      const float *__restrict__ gate, const int32_t *__restrict__ row_cnt,
-                                                      const int32_t *__restrict__ blk, int64_t N, int32_t *__restrict__ keep_ptr,
-                                                      int32_t *__restrict__ keep_ent) {
-  __shared__ int red[kBlock / 64], wtot[kBlock / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__device__ __forceinline__ int blocks_before(const int32_t *__restrict__ blk) {         // sum of blk[0 .. blockIdx.x), in every thread
+  __shared__ int red[kBlock / 64];
   int before = 0;
   for (int b = threadIdx.x; b < (int)blockIdx.x; b += kBlock) before += blk[b];
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
-  if (lane == 0) red[wave] = before;
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = before;
   __syncthreads();
   before = 0;
   for (int i = 0; i < kBlock / 64; ++i) before += red[i];
-  const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const int c = v < N ? row_cnt[v] : 0;
+  return before;
+}
+__device__ __forceinline__ int block_exclusive_rank(int c) {                            // sum of c over the threads before this one
+  __shared__ int wtot[kBlock / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int incl = c;
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) { const int up = __shfl_up(incl, off, 64); if (lane >= off) incl += up; }
   if (lane == 63) wtot[wave] = incl;
   __syncthreads();
-  int s = before + incl - c;
+  int s = incl - c;
   for (int w = 0; w < wave; ++w) s += wtot[w];
+  return s;
+}
+__global__ __launch_bounds__(kBlock) void keep_count_k(const int32_t *__restrict__ in_ptr, const int32_t *__restrict__ in_ent,
+                                                       const float *__restrict__ gate, int64_t N, int32_t *__restrict__ row_cnt,
+                                                       int32_t *__restrict__ blk) {
+  const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  int c = 0;
+  if (v < N) {
+    for (int q = in_ptr[v], hi = in_ptr[v + 1]; q < hi; ++q) c += gate[in_ent[q] >> 1] != 0.f;
+    row_cnt[v] = c;
+  }
+  block_total_to(c, blk);
+}
+__global__ __launch_bounds__(kBlock) void keep_fill_k(const int32_t *__restrict__ in_ptr, const int32_t *__restrict__ in_ent,
+                                                      const float *__restrict__ gate, const int32_t *__restrict__ row_cnt,
+                                                      const int32_t *__restrict__ blk, int64_t N, int32_t *__restrict__ keep_ptr,
+                                                      int32_t *__restrict__ keep_ent) {
+  const int before = blocks_before(blk);
+  const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  int s = before + block_exclusive_rank(v < N ? row_cnt[v] : 0);
   if (v < N) {
     keep_ptr[v] = s;
     for (int q = in_ptr[v], hi = in_ptr[v + 1]; q < hi; ++q) {
@@ -1074,7 +989,6 @@ __global__ __launch_bounds__(kBlock) void keep_count_g_k(const int32_t *__restri
                                                          const float *__restrict__ gate, int64_t N, int32_t *__restrict__ row_cnt,
                                                          int32_t *__restrict__ blk) {
   constexpr int RPB = kBlock / G;
-  __shared__ int red[kBlock / 64];
   const int64_t v = (int64_t)blockIdx.x * RPB + threadIdx.x / G;
   const int gl = threadIdx.x % G;
   int c = 0;
@@ -1084,11 +998,7 @@ __global__ __launch_bounds__(kBlock) void keep_count_g_k(const int32_t *__restri
 #pragma unroll
   for (int off = G / 2; off > 0; off >>= 1) rc += __shfl_xor(rc, off, G);
   if (v < N && gl == 0) row_cnt[v] = rc;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) { int t = 0; for (int i = 0; i < kBlock / 64; ++i) t += red[i]; blk[blockIdx.x] = t; }
+  block_total_to(c, blk);
 }
 template <int G>
 __global__ __launch_bounds__(kBlock) void keep_fill_g_k(const int32_t *__restrict__ in_ptr, const int32_t *__restrict__ in_ent,
@@ -1097,13 +1007,8 @@ __global__ __launch_bounds__(kBlock) void keep_fill_g_k(const int32_t *__restric
                                                         int32_t *__restrict__ keep_ent) {
   constexpr int RPB = kBlock / G;
   static_assert(RPB <= 64 && G <= 32, "one wave scans the block's rows; a group's ballot bits fit a word");
-  __shared__ int red[kBlock / 64], rstart[RPB];
+  __shared__ int rstart[RPB];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int before = 0;
-  for (int b = threadIdx.x; b < (int)blockIdx.x; b += kBlock) before += blk[b];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
-  if (lane == 0) red[wave] = before;
   if (wave == 0) {                                               // exclusive scan of the block's row counts (RPB <= 64 rows: one wave)
     const int64_t vr = (int64_t)blockIdx.x * RPB + lane;
     const int c = (lane < RPB && vr < N) ? row_cnt[vr] : 0;
@@ -1112,9 +1017,7 @@ __global__ __launch_bounds__(kBlock) void keep_fill_g_k(const int32_t *__restric
     for (int off = 1; off < 64; off <<= 1) { const int up = __shfl_up(incl, off, 64); if (lane >= off) incl += up; }
     if (lane < RPB) rstart[lane] = incl - c;
   }
-  __syncthreads();
-  before = 0;
-  for (int i = 0; i < kBlock / 64; ++i) before += red[i];
+  const int before = blocks_before(blk);                         // (its barrier also publishes rstart)
   const int g = threadIdx.x / G, gl = threadIdx.x % G;
   const int64_t v = (int64_t)blockIdx.x * RPB + g;
   if (v >= N) return;                                            // (whole groups: the ballots below see whole groups of their wave)
@@ -1144,7 +1047,6 @@ __global__ __launch_bounds__(kBlock) void inc_keep_count_k(const int32_t *__rest
                                                            const float *__restrict__ gate, const int32_t *__restrict__ list,
                                                            const int32_t *__restrict__ count, int32_t *__restrict__ row_cnt,
                                                            int32_t *__restrict__ blk) {
-  __shared__ int red[kBlock / 64];
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t n = *count;
   int c = 0;
@@ -1155,11 +1057,7 @@ __global__ __launch_bounds__(kBlock) void inc_keep_count_k(const int32_t *__rest
       for (int q = out_ptr[v], hi = out_ptr[v + 1]; q < hi; ++q) c += gate[out_ent[q] >> 1] != 0.f;
     row_cnt[i] = c;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) { int t = 0; for (int k = 0; k < kBlock / 64; ++k) t += red[k]; blk[blockIdx.x] = t; }
+  block_total_to(c, blk);
 }
 __global__ __launch_bounds__(kBlock) void inc_keep_fill_k(const int32_t *__restrict__ in_ptr, const int32_t *__restrict__ in_ent,
                                                           const int32_t *__restrict__ out_ptr, const int32_t *__restrict__ out_ent,
@@ -1167,26 +1065,10 @@ __global__ __launch_bounds__(kBlock) void inc_keep_fill_k(const int32_t *__restr
                                                           const int32_t *__restrict__ count, const int32_t *__restrict__ row_cnt,
                                                           const int32_t *__restrict__ blk, int32_t *__restrict__ keep_ptr,
                                                           int32_t *__restrict__ keep_ent) {
-  __shared__ int red[kBlock / 64], wtot[kBlock / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int before = 0;
-  for (int b = threadIdx.x; b < (int)blockIdx.x; b += kBlock) before += blk[b];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
-  if (lane == 0) red[wave] = before;
-  __syncthreads();
-  before = 0;
-  for (int k = 0; k < kBlock / 64; ++k) before += red[k];
+  const int before = blocks_before(blk);
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t n = *count;
-  const int c = i < n ? row_cnt[i] : 0;
-  int incl = c;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const int up = __shfl_up(incl, off, 64); if (lane >= off) incl += up; }
-  if (lane == 63) wtot[wave] = incl;
-  __syncthreads();
-  int s = before + incl - c;
-  for (int w = 0; w < wave; ++w) s += wtot[w];
+  int s = before + block_exclusive_rank(i < n ? row_cnt[i] : 0);
   if (i < n) {
     keep_ptr[i] = s;
     const int v = list[i];
@@ -1546,6 +1428,30 @@ using namespace dmp;
     if (e_ != hipSuccess) { set_last_hip_error(e_); return DMP_ERR_HIP; } \
   } while (0)
 
+// The CSR build of slots [0, Y) of `p` (Y = 1: one key array; Y = 2: by destination and by source), whose cnt / tiles this
+// lays out in ws: Y counter arrays of N words, then Y tile arrays (dmp_csr_workspace_words / dmp_csr_pair_workspace_words).
+// Every memset and every grid covers Y slots and no more.
+static int csr_build_slots(CsrSlots &p, int Y, const uint8_t *flag, int64_t E, int64_t N, int32_t *ws, hipStream_t st) {
+  if (E >= ((int64_t)1 << 30) || N >= ((int64_t)1 << 31) - 1) return DMP_ERR_UNSUPPORTED;
+  const int64_t ntiles = scan_tiles_for(N);                     // (the layout keeps one spare tile per array)
+  for (int y = 0; y < Y; ++y) { p.cnt[y] = ws + y * N; p.tiles[y] = ws + Y * N + y * ntiles; }
+  DMP_HIP_TRY(hipMemsetAsync(p.status, 0, Y * sizeof(int32_t), st));
+  if (N > 0) DMP_HIP_TRY(hipMemsetAsync(ws, 0, sizeof(int32_t) * (size_t)(Y * N), st));
+  if (E > 0) csr_count_k<<<dim3(nblk(E), Y), kBlock, 0, st>>>(p, E, N);   // (N == 0: every key is out of range, status = 1)
+  if (N == 0) {
+    for (int y = 0; y < Y; ++y) DMP_HIP_TRY(hipMemsetAsync(p.rowptr[y], 0, sizeof(int32_t), st));
+    return check_launch();
+  }
+  const int64_t nt = (N + kScanTile - 1) / kScanTile;           // tiles in use
+  csr_scan_tiles_k<<<dim3((unsigned)nt, Y), kBlock, 0, st>>>(p, N);
+  csr_scan_totals_k<<<dim3(1, Y), kBlock, 0, st>>>(p, nt, N);
+  // (one tile and no edges: its offset is 0 and nothing reads a cursor)
+  if (nt > 1 || E > 0) csr_scan_finish_k<<<dim3((unsigned)nt, Y), kBlock, 0, st>>>(p, N);
+  if (E > 0) csr_fill_k<<<dim3(nblk(E), Y), kBlock, 0, st>>>(p, flag, E, N);
+  csr_sort_rows_k<<<dim3(nblk(N), Y), kBlock, 0, st>>>(p, N);
+  return check_launch();
+}
+
 extern "C" {
 
 size_t dmp_csr_workspace_words(int64_t N, int64_t E) {
@@ -1566,34 +1472,14 @@ int dmp_csr_build_pair(const int64_t *dst, const int64_t *src, const uint8_t *fl
                        int32_t *status, int32_t *ws, void *stream) {
   if (E < 0 || N < 0 || !in_ptr || !out_ptr || !status || !ws) return DMP_ERR_BAD_ARG;
   if (E > 0 && (!dst || !src || !in_ent || !out_ent)) return DMP_ERR_BAD_ARG;
-  if (E >= ((int64_t)1 << 30) || N >= ((int64_t)1 << 31) - 1) return DMP_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t ntiles = scan_tiles_for(N);
-  CsrPair p;
+  CsrSlots p = {};
   p.key[0] = dst; p.key[1] = src;
   p.rowptr[0] = in_ptr; p.rowptr[1] = out_ptr;
   p.ent[0] = in_ent; p.ent[1] = out_ent;
   p.key32[0] = dst32; p.key32[1] = src32;
   p.degree[0] = in_deg; p.degree[1] = out_deg;
-  p.cnt[0] = ws; p.cnt[1] = ws + N;
-  p.tiles[0] = ws + 2 * N; p.tiles[1] = ws + 2 * N + ntiles;
   p.status = status;
-  DMP_HIP_TRY(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), st));
-  if (N == 0) {
-    DMP_HIP_TRY(hipMemsetAsync(in_ptr, 0, sizeof(int32_t), st));
-    DMP_HIP_TRY(hipMemsetAsync(out_ptr, 0, sizeof(int32_t), st));
-    if (E > 0) DMP_HIP_TRY(hipMemsetAsync(status, 0x01, 2 * sizeof(int32_t), st));   // every endpoint is out of range
-    return DMP_OK;
-  }
-  DMP_HIP_TRY(hipMemsetAsync(ws, 0, sizeof(int32_t) * (size_t)(2 * N), st));
-  const int64_t nt = (N + kScanTile - 1) / kScanTile;           // tiles in use (the layout keeps one spare per array)
-  if (E > 0) csr_count_pair<<<dim3(nblk(E), 2), kBlock, 0, st>>>(p, E, N);
-  scan_tiles_pair<<<dim3((unsigned)nt, 2), kBlock, 0, st>>>(p, N);
-  scan_tile_sums_pair<<<dim3(1, 2), kBlock, 0, st>>>(p, nt, N);
-  scan_finish_pair<<<dim3((unsigned)nt, 2), kBlock, 0, st>>>(p, N);
-  if (E > 0) csr_fill_pair<<<dim3(nblk(E), 2), kBlock, 0, st>>>(p, flag, E, N);
-  csr_sort_rows_pair<<<dim3(nblk(N), 2), kBlock, 0, st>>>(p, N);
-  return check_launch();
+  return csr_build_slots(p, 2, flag, E, N, ws, (hipStream_t)stream);
 }
 
 int dmp_csr_build_graphs_max_nodes(void) { return kCsrGraphNodes; }
@@ -1618,20 +1504,10 @@ int dmp_csr_build(const int64_t *key, const uint8_t *flag, int64_t E, int64_t N,
                   void *stream) {
   if (E < 0 || N < 0 || !rowptr || !status || !ws) return DMP_ERR_BAD_ARG;
   if (E > 0 && (!key || !ent)) return DMP_ERR_BAD_ARG;
-  if (E >= ((int64_t)1 << 30) || N >= ((int64_t)1 << 31) - 1) return DMP_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  int32_t *cnt = ws, *tiles = ws + N;
-  DMP_HIP_TRY(hipMemsetAsync(status, 0, sizeof(int32_t), st));
-  if (N > 0) DMP_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)N, st));
-  if (E > 0) csr_count<<<nblk(E), kBlock, 0, st>>>(key, E, N, cnt, key32, status);
-  int rc = exclusive_scan<int32_t, int32_t>(cnt, N, rowptr, tiles, st);
-  if (rc != DMP_OK) return rc;
-  if (N > 0 && E > 0) {
-    copy_i32<<<nblk(N), kBlock, 0, st>>>(rowptr, N, cnt);  // cnt becomes the fill cursor
-    csr_fill<<<nblk(E), kBlock, 0, st>>>(key, flag, E, N, cnt, ent);
-  }
-  if (N > 0) csr_sort_rows<<<nblk(N), kBlock, 0, st>>>(rowptr, N, ent, degree);
-  return check_launch();
+  CsrSlots p = {};
+  p.key[0] = key; p.rowptr[0] = rowptr; p.ent[0] = ent; p.key32[0] = key32; p.degree[0] = degree;
+  p.status = status;
+  return csr_build_slots(p, 1, flag, E, N, ws, (hipStream_t)stream);
 }
 
 int dmp_incidence_build(const int32_t *in_ptr, const int32_t *in_ent, const int32_t *out_ptr,
@@ -1662,34 +1538,6 @@ int dmp_exclusive_scan_i64(const int64_t *in, int64_t n, int64_t *out, int64_t *
   return exclusive_scan<int64_t, int64_t>(in, n, out, ws, (hipStream_t)stream);
 }
 
-int dmp_collate(const int64_t *local_src, const int64_t *local_dst, const int64_t *num_nodes,
-                const int64_t *num_edges, int64_t B, int64_t N, int64_t E, int64_t *node_off,
-                int64_t *edge_off, int64_t *src, int64_t *dst, int32_t *edge_graph,
-                int32_t *node_graph, void *stream) {
-  if (B < 0 || N < 0 || E < 0 || !node_off || !edge_off) return DMP_ERR_BAD_ARG;
-  if (B > 0 && (!num_nodes || !num_edges)) return DMP_ERR_BAD_ARG;
-  if (E > 0 && (!local_src || !local_dst || !src || !dst || B == 0)) return DMP_ERR_BAD_ARG;
-  if (B > kScanTile) {
-    // sizes are scanned by single-tile launches below (no scratch in the signature)
-    return DMP_ERR_UNSUPPORTED;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (B == 0) {
-    DMP_HIP_TRY(hipMemsetAsync(node_off, 0, sizeof(int64_t), st));
-    DMP_HIP_TRY(hipMemsetAsync(edge_off, 0, sizeof(int64_t), st));
-    return DMP_OK;
-  }
-  // B <= 2048: one tile each; the tile total lands in off[B] twice (harmless)
-  collate_offsets<<<dim3(1, 2), kBlock, 0, st>>>(num_nodes, num_edges, B, node_off, edge_off);
-  const bool nodes = node_graph && N > 0;
-  if (E > 0 || nodes) {
-    const int64_t most = (nodes && N > E) ? N : (E > 0 ? E : N);
-    collate_both<<<dim3(nblk(most), nodes ? 2 : 1), kBlock, 0, st>>>(local_src, local_dst, node_off, edge_off, B, E, N, src, dst,
-                                                                   edge_graph, node_graph);
-  }
-  return check_launch();
-}
-
 int dmp_collate_jobs(const dmp_collate_job *jobs, int n, void *stream) {
   if (!jobs || n < 1 || n > DMP_COLLATE_MAX_JOBS) return DMP_ERR_BAD_ARG;
   CollateJobs t;
@@ -1698,15 +1546,33 @@ int dmp_collate_jobs(const dmp_collate_job *jobs, int n, void *stream) {
     const dmp_collate_job &j = jobs[i];
     if (j.B <= 0 || j.N < 0 || j.E < 0 || !j.node_off || !j.edge_off || !j.num_nodes || !j.num_edges) return DMP_ERR_BAD_ARG;
     if (j.E > 0 && (!j.local_src || !j.local_dst || !j.src || !j.dst)) return DMP_ERR_BAD_ARG;
-    if (j.B > kScanTile) return DMP_ERR_UNSUPPORTED;         // sizes are scanned by single-tile launches, as in dmp_collate
+    if (j.B > kScanTile) return DMP_ERR_UNSUPPORTED;         // sizes are scanned by single-tile launches (no scratch in the job)
     t.job[i] = j;
-    const int64_t m = j.E > j.N ? j.E : j.N;
+    const int64_t rows = j.node_graph ? j.N : 0;             // (a job without node_graph has no node pass to size the grid for)
+    const int64_t m = j.E > rows ? j.E : rows;
     if (m > most) most = m;
   }
   hipStream_t st = (hipStream_t)stream;
   collate_offsets_jobs<<<dim3(1, 2 * n), kBlock, 0, st>>>(t);
   if (most > 0) collate_both_jobs<<<dim3(nblk(most), 2 * n), kBlock, 0, st>>>(t);
   return check_launch();
+}
+
+// one batch: a single job, but for the batch without graphs, which only this entry point admits
+int dmp_collate(const int64_t *local_src, const int64_t *local_dst, const int64_t *num_nodes,
+                const int64_t *num_edges, int64_t B, int64_t N, int64_t E, int64_t *node_off,
+                int64_t *edge_off, int64_t *src, int64_t *dst, int32_t *edge_graph,
+                int32_t *node_graph, void *stream) {
+  if (B < 0 || N < 0 || E < 0 || !node_off || !edge_off) return DMP_ERR_BAD_ARG;
+  if (B == 0) {
+    if (E > 0) return DMP_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    DMP_HIP_TRY(hipMemsetAsync(node_off, 0, sizeof(int64_t), st));
+    DMP_HIP_TRY(hipMemsetAsync(edge_off, 0, sizeof(int64_t), st));
+    return DMP_OK;
+  }
+  const dmp_collate_job j{local_src, local_dst, num_nodes, num_edges, B, N, E, node_off, edge_off, src, dst, edge_graph, node_graph};
+  return dmp_collate_jobs(&j, 1, stream);
 }
 
 int dmp_add_reversed_edges(const int64_t *src, const int64_t *dst, const int64_t *eid,
@@ -1816,14 +1682,6 @@ int dmp_pool_index_jobs(const dmp_pool_job *jobs, int n, void *stream) {
   pool_offsets_k<<<(unsigned)n, kBlock, 0, st>>>(t);
   pool_fill_k<<<dim3((unsigned)nblk(most), (unsigned)n), kBlock, 0, st>>>(t);
   return check_launch();
-}
-
-int dmp_pool_index(const int64_t *sizes_a, int64_t Ba, const int64_t *sizes_b, int64_t Bb, const uint8_t *flag_a,
-                   const uint8_t *flag_b, int64_t rows_a, int64_t R, int chunk, int64_t *off, int32_t *gptr, int32_t *vptr,
-                   int32_t *vent, int32_t *gent, int32_t *seg, void *stream) {
-  dmp_pool_job j{sizes_a, sizes_b, Ba, Bb, flag_a, flag_b, rows_a, R, chunk, off, gptr, vptr, vent, gent, seg, nullptr, nullptr,
-                 nullptr};
-  return dmp_pool_index_jobs(&j, 1, stream);
 }
 
 int dmp_pool_weight_sums(const float *w, const uint8_t *flag8, const int64_t *off, int64_t B, float *out, void *stream) {

@@ -78,10 +78,10 @@ int dmp_csr_build(const int64_t *key, const uint8_t *flag, int64_t num_edges,
                   int32_t *ws, void *stream);
 
 /*
- * Both CSRs of a graph -- by destination (in_*) and by source (out_*) -- built side by side: the same arrays two
- * dmp_csr_build calls produce (rows in ascending edge id, entry = eid << 1 | flag), with the dispatches of a build paid
- * once for the pair.  status: [2] (bit 0 of status[0] / status[1]: a dst / src endpoint outside [0, N)).
- * ws: dmp_csr_pair_workspace_words(N) int32 words.
+ * Both CSRs of a graph -- by destination (in_*) and by source (out_*) -- built side by side by the dispatches of one build
+ * (rows in ascending edge id, entry = eid << 1 | flag): every kernel of the build takes its key array from blockIdx.y, and
+ * dmp_csr_build is the same build with one key array.  status: [2], each word 0, or 1 if a dst (status[0]) / src (status[1])
+ * endpoint was outside [0, N).  ws: dmp_csr_pair_workspace_words(N) int32 words.
  */
 size_t dmp_csr_pair_workspace_words(int64_t num_nodes);
 int dmp_csr_build_pair(const int64_t *dst, const int64_t *src, const uint8_t *flag, int64_t num_edges, int64_t num_nodes,
@@ -277,13 +277,8 @@ int dmp_sample_in_edges(const int32_t *in_ptr, const int32_t *in_ent, const uint
  * the sum; NULL = 0), seg[r] = the graph of row r (optional).  sizes and flags come as TWO pieces each (the pattern graphs
  * then the target graphs of a union pass: B = Ba + Bb, rows [0, rows_a) read flag_a).  off [B+1] int64, gptr [B+1],
  * vptr [V+1], vent [R], gent [V], seg [R] int32.  Two launches, no host synchronisation.
- */
-int dmp_pool_index(const int64_t *sizes_a, int64_t Ba, const int64_t *sizes_b, int64_t Bb,
-                   const uint8_t *flag_a, const uint8_t *flag_b, int64_t rows_a, int64_t R, int chunk,
-                   int64_t *off, int32_t *gptr, int32_t *vptr, int32_t *vent, int32_t *gent, int32_t *seg,
-                   void *stream);
-
-/* Several pooling indexes in the same two launches (a step needs the node index and the edge index of its batch), with
+ *
+ * One or several indexes in the same two launches (a step needs the node index and the edge index of its batch), with
  * three optional outputs per index: flag8 [R] = the flags of both pieces back to back (0 / 1), rowmap [R] = seg[r], or -1
  * for a flagged row (the rows the pooled heads mask out, basemodel.py:1521-1531), sizes [Ba + Bb] = both size pieces back
  * to back.  `jobs` is a HOST array. */

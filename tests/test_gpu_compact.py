@@ -292,6 +292,7 @@ def test_pool_indexes_built_together_equal_the_single_builds():
 
 
 def test_collate_many_equals_collate_device():
+    import graph_oracle as GO
     from dualmessagepassing_amd.collate import collate_device, collate_device_many
     gpu = th.device("cuda:0")
     rng = np.random.default_rng(3)
@@ -306,14 +307,27 @@ def test_collate_many_equals_collate_device():
                          total_edges=int(ne.sum()), ndata={"x": t(np.arange(nn.sum()))}, edata={}, max_nodes=int(nn.max()),
                          max_edges=int(max(ne.max(), 1))))
     many = collate_device_many(jobs)
+    names = ("_src", "_dst", "node_offsets", "edge_offsets", "edge_graph", "node_graph")
     for j, g in zip(jobs, many):
         one = collate_device(j["local_src"], j["local_dst"], j["num_nodes"], j["num_edges"], j["total_nodes"], j["total_edges"],
                              ndata=j["ndata"], edata=j["edata"], max_nodes=j["max_nodes"], max_edges=j["max_edges"])
-        for k in ("_src", "_dst", "node_graph", "edge_graph", "node_offsets", "edge_offsets"):
+        want = GO.collate(*[j[k].cpu().numpy() for k in ("local_src", "local_dst", "num_nodes", "num_edges")])     # the C oracle
+        for k, w in zip(names, want):
             assert th.equal(getattr(one, k), getattr(g, k)), k
+            assert np.array_equal(getattr(g, k).cpu().numpy(), w) and getattr(g, k).dtype == th.from_numpy(w).dtype, k
+        # without the segment arrays: the rest is the oracle's all the same
+        bare = collate_device(j["local_src"], j["local_dst"], j["num_nodes"], j["num_edges"], j["total_nodes"], j["total_edges"],
+                              with_segments=False)
+        assert bare.node_graph is None and bare.edge_graph is None
+        for k, w in zip(names[:4], want):
+            assert np.array_equal(getattr(bare, k).cpu().numpy(), w), k
         assert (one.max_num_nodes, one.max_num_edges, one.tiling is None, one.node_tiling is None) == \
                (g.max_num_nodes, g.max_num_edges, g.tiling is None, g.node_tiling is None)
         assert g.ndata["x"] is not None and g.batch_size == one.batch_size
+    # a batch without graphs: both offset arrays are [0]
+    none = th.zeros(0, dtype=th.int64, device=gpu)
+    empty = collate_device(none, none, none, none, 0, 0)
+    assert empty.node_offsets.tolist() == [0] and empty.edge_offsets.tolist() == [0] and empty.batch_size == 0
 
 
 @pytest.mark.parametrize("H,R", [(128, 4099), (64, 2051), (128, 31)])

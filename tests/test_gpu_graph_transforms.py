@@ -174,20 +174,39 @@ def test_concat_pairs_bit_exact(gpu):
         assert o.is_cuda and o.dtype == w.dtype and th.equal(o.cpu(), w)
 
 
+def _csr_restated(key, flag, N):
+    """The CSR of one key array as the header states it, in numpy: (rowptr, entries, key32, degree, status)."""
+    valid = (0 <= key) & (key < N)
+    degree = np.bincount(key[valid], minlength=N)
+    rowptr = np.concatenate([[0], np.cumsum(degree)])
+    ent = ((np.arange(len(key)) << 1) | flag)[valid][np.argsort(key[valid], kind="stable")]
+    return (rowptr.astype(np.int32), ent.astype(np.int32), np.where(valid, key, 0).astype(np.int32), degree.astype(np.int64),
+            int(np.any(~valid)))
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("N,E", [(1, 0), (5, 40), (2049, 30000), (73728, 200001)])
+@pytest.mark.parametrize("N,E", [(1, 0), (5, 40), (2049, 30000), (73728, 200001),
+                                 (2048, 5000), (2049, 5000),      # exactly one scan tile, and one past it
+                                 (526337, 4000),                  # 258 scan tiles: the tile totals take a second trip with a carry
+                                 (3, 400), (5, 300),              # rows of ~133 / ~60 entries: the heap-sort / insertion-sort branches
+                                 (0, 3)])                         # no nodes: every key is out of range
 def test_csr_build_pair_equals_two_builds(N, E, gpu):
-    """dmp_csr_build_pair against two dmp_csr_build calls: identical rowptr / entries / 32-bit keys / degrees / status,
-    including out-of-range endpoints (flagged, skipped)."""
+    """dmp_csr_build (once per key) and dmp_csr_build_pair, each against the numpy restatement of the CSR -- rowptr / entries /
+    32-bit keys / degrees / status, including out-of-range endpoints (flagged, skipped), nothing written beyond them -- and
+    against each other; and dmp_csr_build with flag / key32 / degree NULL: flag bit 0, one status word written."""
     import torch as th
     from dualmessagepassing_amd import _lib
     lib = _lib.load()
     g = th.Generator().manual_seed(N + E)
-    src = th.randint(0, N, (E,), generator=g)
-    dst = th.randint(0, N, (E,), generator=g)
+    if N == 0:
+        src, dst = th.tensor([0, 5, -2]), th.tensor([1, -1, 0])  # arbitrary
+    else:
+        src = th.randint(0, N, (E,), generator=g)
+        dst = th.randint(0, N, (E,), generator=g)
     if E > 10:
         dst[3], src[7] = N + 5, -1                               # out of range: status bit, no entry
     flag = (th.rand(E, generator=g) < 0.5).to(th.uint8)
+    want = [_csr_restated(k.numpy(), flag.numpy(), N) for k in (dst, src)]
     src, dst, flag = src.cuda(), dst.cuda(), flag.cuda()
     i32 = dict(dtype=th.int32, device="cuda")
     mk = lambda: (th.full((N + 1,), -1, **i32), th.full((E,), -1, **i32), th.full((E,), -1, **i32),
@@ -206,6 +225,25 @@ def test_csr_build_pair_equals_two_builds(N, E, gpu):
     for a, b in zip(single, pair):
         valid = int(a[0][N])                                      # entries past the valid ones are never written
         assert th.equal(a[0], b[0]) and th.equal(a[1][:valid], b[1][:valid]) and th.equal(a[2], b[2]) and th.equal(a[3], b[3])
+    # each build against the restatement
+    for built, st in ((single, st1), (pair, st2)):
+        assert st.tolist() == [w[4] for w in want]
+        for o, w in zip(built, want):
+            valid = int(w[0][N])
+            assert np.array_equal(o[0].cpu().numpy(), w[0]) and np.array_equal(o[1][:valid].cpu().numpy(), w[1])
+            assert bool((o[1][valid:] == -1).all())
+            assert np.array_equal(o[2].cpu().numpy(), w[2]) and np.array_equal(o[3].cpu().numpy(), w[3])
+    if N == 0:
+        assert st1.tolist() == st2.tolist() == [1, 1] and all(int(o[0][0]) == 0 for o in single + pair)
+    # the optional arrays left out: entries with flag bit 0, the status word behind the build's own untouched
+    bare, st3 = mk(), th.full((2,), 7, **i32)
+    _lib.check(lib.dmp_csr_build(P(dst), None, E, N, P(bare[0]), P(bare[1]), None, None, P(st3), P(ws), _lib.stream_ptr()),
+               "dmp_csr_build")
+    w = _csr_restated(dst.cpu().numpy(), np.zeros(E, np.int64), N)
+    valid = int(w[0][N])
+    assert np.array_equal(bare[0].cpu().numpy(), w[0]) and np.array_equal(bare[1][:valid].cpu().numpy(), w[1])
+    assert bool((bare[1][valid:] == -1).all()) and bool((bare[2] == -1).all()) and bool((bare[3] == -1).all())
+    assert st3.tolist() == [w[4], 7]
 
 
 def test_dual_subisomorphisms_match_reference_and_oracle(gpu):

@@ -124,6 +124,41 @@ def test_scatter_adds_leave_out_the_dead_nodes_rows(H, gpu):
     assert int(kp[200].item()) == want and int(kp[n].item()) <= 2 * int((e_gate != 0).sum())
 
 
+def test_kept_incidence_is_the_gated_merge_of_every_kept_node(gpu):
+    """``NodeRows.kept_incidence`` (dmp_incidence_keep) against the same merge written in numpy, both forms (in- and out-entries;
+    ``in_only``): 1000 nodes of which about 450 are kept -- two blocks of rows, the second ragged -- under an edge gate that keeps
+    about half the edges, self loops among them (their in-entry comes first)."""
+    from dualmessagepassing_amd import fused, gatememo
+    from dualmessagepassing_amd.graph import GraphIndex
+    rng = np.random.default_rng(11)
+    N, E = 1000, 6000
+    src, dst = rng.integers(0, N, E), rng.integers(0, N, E)
+    src[:40:4] = dst[:40:4]
+    rev, keep_v, keep_e = rng.random(E) < 0.5, rng.random(N) < 0.45, rng.random(E) < 0.5
+    keep_e[:8] = True
+    kept = np.nonzero(keep_v)[0]
+    assert 300 <= len(kept) <= 600 and len(kept) % 256 != 0
+    t = lambda a: th.from_numpy(a).to(gpu)
+    ix = GraphIndex(t(src), t(dst), N, t(rev))
+    v_gate, e_gate = t(keep_v.astype(np.float32)), t(keep_e.astype(np.float32))
+    for gate in (v_gate, e_gate):
+        gatememo.mark(gate, binary=True, zero_rows=True)
+    vmask = fused.gate_row_mask(v_gate)
+    nd = fused.NodeRows(vmask, fused.kept_rows(vmask, 0, N), None, None)
+    assert nd.rows[0][:len(kept)].tolist() == kept.tolist()
+    ent = (np.arange(E) << 1) | rev
+    for in_only in (False, True):
+        want_ptr, want_ent = [0], []
+        for v in kept:
+            row = [(e, 0, ent[e]) for e in np.nonzero((dst == v) & keep_e)[0]]
+            if not in_only:
+                row += [(e, 1, ent[e] ^ 1) for e in np.nonzero((src == v) & keep_e)[0]]
+            want_ent += [x for _, _, x in sorted(row)]             # ascending edge id, an edge's in-entry before its out-entry
+            want_ptr.append(len(want_ent))
+        kp, ke = nd.kept_incidence(ix, e_gate, in_only=in_only)
+        assert kp[:len(kept) + 1].tolist() == want_ptr and ke[:want_ptr[-1]].tolist() == want_ent, in_only
+
+
 @pytest.mark.parametrize("H", [128, 64])
 def test_tile_kernel_accumulates_and_activates_on_the_kept_nodes(H, gpu):
     """``out_fwd_typed`` on the kept nodes' tiles: a K = 3H product as three launches accumulating onto their own output with
