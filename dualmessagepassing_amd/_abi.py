@@ -422,4 +422,6 @@ SIGNATURES = {
                                  c_ptr, c_ptr, c_ptr, c_ptr]),
     "dmp_collate_resident": (c_int, [_p(dmp_resident_side), c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, _p(dmp_resident_batch), c_ptr, c_ptr,
                                      c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
+    "dmp_eval_terms": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
+                               c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
 }

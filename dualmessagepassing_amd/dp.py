@@ -523,10 +523,13 @@ class StepGraph:
 
     MAX_SEEN = 1024      # signatures remembered as "seen once" (oldest forgotten first)
 
-    def __init__(self, fn, optimizer=None, max_shapes=4):
+    def __init__(self, fn, optimizer=None, max_shapes=4, stream=None):
+        """``stream``: the side stream of another ``StepGraph`` (its ``.stream``) to run on instead of one of this object's
+        own -- two objects whose steps touch the same state (a training and an evaluation step of one model) then record
+        on ONE stream, and a loop under either's ``on_stream()`` is under both's."""
         self.fn, self.optimizer, self.max_shapes = fn, optimizer, int(max_shapes)
         self._seen, self._graphs = OrderedDict(), {}
-        self._stream = None
+        self._stream = stream
         self.replays = self.eager_calls = 0
 
     @staticmethod

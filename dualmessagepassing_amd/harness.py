@@ -846,7 +846,78 @@ def train_epoch(model, optimizer, dataset, batch_size, device, sync=None, bp_los
     return {"bp_loss": float(tot_loss / max(cnt, 1)), "eval_metric": float(tot_eval / max(cnt, 1))}
 
 
-class GraphedTrainStep:
+class _RecordedStep:
+    """What the recorded steps (``GraphedTrainStep``, ``GraphedEvalStep``) share, each rule stated once: which models a
+    recording takes, when and how a batch is padded, and the capacities (subisomorphism rows, LRP permutation indexes)
+    that keep a batch's tensors at a shape the recording has seen."""
+
+    _EAGER = "runs eagerly"          # how the refusal of an edge-sequence model names the eager route
+
+    def _init_shared(self, model, max_shapes, pad, match_weights, exact_shapes=False):
+        """``exact_shapes``: a step that reads every row of the batch (the representation regulariser) is never padded;
+        neither is a model with BatchNorm layers (their statistics would see the inert rows)."""
+        from .seqmodel import EdgeSeqModel
+        if isinstance(model, EdgeSeqModel):
+            raise ValueError("%s records the graph models' steps only: %s (an edge-sequence model) %s"
+                             % (type(self).__name__, type(model).__name__, self._EAGER))
+        self.model = model
+        if isinstance(match_weights, str):
+            match_weights = match_weights.split(",")
+        self.match_weights = tuple(w for w in ("node", "edge") if w in (match_weights or ()))
+        self._sub_caps = {}
+        self._perm_caps = {}
+        self.dataset_cls = None
+        self.pad, self._pad_spec = pad, None
+        if pad and (exact_shapes or any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for m in model.modules())):
+            self.pad = None
+        self.max_shapes = int(max_shapes)
+
+    def _padding(self, dataset, indices):
+        """The dataset's padding layout (``pad_buckets``), decided at the first batch: the batch size is that batch's."""
+        if self.pad and self._pad_spec is None:
+            ragged = len({(int(x[k]["num_nodes"]), len(x[k]["src"])) for x in dataset.samples for k in ("pattern", "graph")}) > 2
+            self._pad_spec = dataset.pad_buckets(len(indices), levels=self.max_shapes) if (self.pad is True or ragged) else False
+        return self._pad_spec or None
+
+    def _batch_kwargs(self, dataset, indices):
+        """The keyword arguments of ``dataset.batch_arrays`` for this batch: the padding when the batch fits it, the LRP
+        view's permutation capacities (refused outside the device index build) and, with ``match_weights``, the
+        subisomorphism rows' capacity -- one of each per batch size."""
+        self.dataset_cls = type(dataset)
+        if getattr(self, "_samples", None) is not dataset.samples:      # another dataset: a layout and capacities of its own
+            self._samples, self._pad_spec = dataset.samples, None
+            self._sub_caps.clear()
+            self._perm_caps.clear()
+        lrp = hasattr(dataset, "perm_capacity")         # the LRP view: both permutation indexes at a capacity level
+        pad = self._padding(dataset, indices)
+        if pad is not None and len(indices) > pad["batch"]:
+            pad = None
+        kw = {} if pad is None else {"pad": pad}
+        size = pad["batch"] if pad is not None else len(indices)      # one capacity per batch size: what any such batch fits
+        if lrp:
+            from . import _abi
+            if dataset.max_degree > _abi.DMP_LRP_MAX_NEIGHBOURS or not 1 <= dataset.seq_len <= _abi.DMP_LRP_MAX_SEQ_LEN:
+                raise ValueError("%s: a node with %d distinct neighbours / lrp_seq_len %d is outside the device index build "
+                                 "(the host build cannot be recorded): run eagerly"
+                                 % (type(self).__name__, dataset.max_degree, dataset.seq_len))
+            if size not in self._perm_caps:
+                self._perm_caps[size] = dataset.perm_capacity(size, levels=self.max_shapes)
+            kw["perms"] = self._perm_caps[size]
+        if self.match_weights:
+            if size not in self._sub_caps:
+                self._sub_caps[size] = dataset.sub_capacity(size)
+            kw["subs"] = self._sub_caps[size]
+        return kw
+
+    def _subiso(self, meta, pattern, graph, subs):
+        """The batch's ``(node, edge)`` subisomorphism weights on the device from ``(sub_flat, sample_ptr)`` at the dataset's
+        capacity.  The work of the edge-weight kernel (rows x pattern edges) sizes its grid only: a constant of the
+        recording, from the capacity and the largest pattern."""
+        hint = int(subs[0].numel()) * max(1, int(meta[0][3])) // max(1, int(meta[0][2]))
+        return subiso_weights(pattern, graph, subs[0], subs[1], self.match_weights, validate=False, work_hint=hint)
+
+
+class GraphedTrainStep(_RecordedStep):
     """The training step of ``train_epoch`` (collate, forward, count loss and, with ``match_weights``, the subisomorphism
     weights and the matching terms, backward, gradient pack, clipping, AdamW) as ONE HIP graph per batch shape (``dp.StepGraph``): at the reference's own batch size (64 pairs of small
     graphs, config.py) a step is ~150 launches of microseconds each behind ~3 ms of Python, and a replay is a single
@@ -858,6 +929,8 @@ class GraphedTrainStep:
     recordings, run eagerly -- through the same function, so both ways compute the same step.  Run the training loop
     under ``with step.steps.on_stream():`` when it also copies sizeable tensors between host and device (checkpoints,
     predictions): see ``dp.StepGraph`` (``fit(graph=True)`` does)."""
+
+    _EAGER = "trains eagerly (train_epoch without graph=...)"
 
     def __init__(self, model, optimizer, sync, bp_loss="MSE", eval_metric="MAE", max_grad_norm=8.0, with_rep_reg=False,
                  max_shapes=4, pad="auto", match_weights=()):
@@ -875,29 +948,16 @@ class GraphedTrainStep:
         in this order its last three are the contiguous coefficient triple ``dmp_match_loss`` reads.  Nothing outside this
         class reads it."""
         from .dp import StepGraph
-        from .seqmodel import EdgeSeqModel
-        if isinstance(model, EdgeSeqModel):
-            raise ValueError("GraphedTrainStep records the graph models' steps only: %s (an edge-sequence model) trains "
-                             "eagerly (train_epoch without graph=...)" % type(model).__name__)
+        self._init_shared(model, max_shapes, pad, match_weights, exact_shapes=with_rep_reg)
         if getattr(sync, "world", 1) != 1:
             raise ValueError("GraphedTrainStep records single-rank steps only")
         if not getattr(optimizer, "capturable", False):
             raise ValueError("GraphedTrainStep needs FlatAdamW(capturable=True)")
-        self.model, self.optimizer, self.sync = model, optimizer, sync
+        self.optimizer, self.sync = optimizer, sync
         self.bp, self.ev, self.max_grad_norm, self.with_rep_reg = _CRIT[bp_loss], _CRIT[eval_metric], max_grad_norm, with_rep_reg
-        if isinstance(match_weights, str):
-            match_weights = match_weights.split(",")
-        self.match_weights = tuple(w for w in ("node", "edge") if w in (match_weights or ()))
         self.bp_name = bp_loss
-        self._sub_caps = {}
-        self._perm_caps = {}
         self.hyper = None
         self._hyper_host = None
-        self.dataset_cls = None
-        self.pad, self._pad_spec = pad, None
-        if pad and (with_rep_reg or any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for m in model.modules())):
-            self.pad = None
-        self.max_shapes = int(max_shapes)
         self.steps = StepGraph(self._step, optimizer=optimizer, max_shapes=max_shapes)
 
     def _step(self, meta, *tensors):
@@ -923,12 +983,9 @@ class GraphedTrainStep:
                       for k in ("p_v_rep", "p_e_rep", "g_v_rep", "g_e_rep") if out[k] is not None)
             loss = loss + hyper[0] * reg
         if subs:
-            # the work of the edge-weight kernel (rows x pattern edges) sizes its grid only: a constant of the recording,
-            # from the capacity and the largest pattern
-            hint = int(subs[0].numel()) * max(1, int(meta[0][3])) // max(1, int(meta[0][2]))
             with torch.no_grad():
-                node_w, edge_w = subiso_weights(pattern, graph, subs[0], subs[1], self.match_weights, validate=False, work_hint=hint)
-                if edge_w is not None:                         # train.py:636-641 (the graph models' is the identity)
+                node_w, edge_w = self._subiso(meta, pattern, graph, subs)
+                if edge_w is not None:                        # train.py:636-641 (the graph models' is the identity)
                     edge_w = self.model.refine_edge_weights(edge_w)
             for w, pk, mk in ((node_w, "pred_v", "g_v_mask"), (edge_w, "pred_e", "g_e_mask")):
                 if w is not None and out[pk] is not None:
@@ -944,39 +1001,12 @@ class GraphedTrainStep:
                 return loss.detach(), (self.ev(F.relu(pred), counts, reduction="none") * weights).sum() / weights.sum()
             return loss.detach(), self.ev(F.relu(pred), counts)
 
-    def _padding(self, dataset, indices):
-        """The dataset's padding layout (``pad_buckets``), decided at the first batch: the batch size is that batch's."""
-        if self.pad and self._pad_spec is None:
-            ragged = len({(int(x[k]["num_nodes"]), len(x[k]["src"])) for x in dataset.samples for k in ("pattern", "graph")}) > 2
-            self._pad_spec = dataset.pad_buckets(len(indices), levels=self.max_shapes) if (self.pad is True or ragged) else False
-        return self._pad_spec or None
-
     def __call__(self, dataset, indices, device, neg_slp=0.0, rep_reg_w=0.0, match_loss_w=0.0, match_reg_w=0.0):
         if rep_reg_w > 0 and not self.with_rep_reg:
             raise ValueError("GraphedTrainStep(with_rep_reg=True) to train with the representation regulariser")
         if (match_loss_w > 0 or match_reg_w > 0) and not self.match_weights:
             raise ValueError("GraphedTrainStep(match_weights=...) to train with the matching terms")
-        self.dataset_cls = type(dataset)
-        lrp = hasattr(dataset, "perm_capacity")          # the LRP view: both permutation indexes at a capacity level
-        pad = self._padding(dataset, indices)
-        if pad is not None and len(indices) > pad["batch"]:
-            pad = None
-        kw = {} if pad is None else {"pad": pad}
-        if lrp:
-            from . import _abi
-            if dataset.max_degree > _abi.DMP_LRP_MAX_NEIGHBOURS or not 1 <= dataset.seq_len <= _abi.DMP_LRP_MAX_SEQ_LEN:
-                raise ValueError("GraphedTrainStep: a node with %d distinct neighbours / lrp_seq_len %d is outside the device "
-                                 "index build (the host build cannot be recorded): train eagerly" % (dataset.max_degree, dataset.seq_len))
-            size = pad["batch"] if pad is not None else len(indices)
-            if size not in self._perm_caps:
-                self._perm_caps[size] = dataset.perm_capacity(size, levels=self.max_shapes)
-            kw["perms"] = self._perm_caps[size]
-        if self.match_weights:
-            size = pad["batch"] if pad is not None else len(indices)      # one capacity per batch size: what any such batch fits
-            if size not in self._sub_caps:
-                self._sub_caps[size] = dataset.sub_capacity(size)
-            kw["subs"] = self._sub_caps[size]
-        meta, tensors = dataset.batch_arrays(indices, device, **kw)
+        meta, tensors = dataset.batch_arrays(indices, device, **self._batch_kwargs(dataset, indices))
         if self.hyper is None:
             self.hyper = torch.zeros(4, dtype=torch.float32, device=device)
         host = (float(rep_reg_w), float(neg_slp), float(match_loss_w), float(match_reg_w))
@@ -998,14 +1028,253 @@ def binary_auc(target, pred):
     return 0.5 * (int((t & p).sum()) / pos + int((~t & ~p).sum()) / neg)
 
 
+class EvalBuffers:
+    """What ``eval_terms`` writes for one evaluation pass, all on ``device``: ``rows`` [4, cap] fp32 -- ``pred`` (row 0),
+    ``target`` (1) and the two matching heads' per-pair errors ``err`` (2: node, 3: edge) --, ``cursor`` int64 [1] (the rows
+    written so far), ``sums`` float64 [4] (pairs, sum |e|, sum e^2, sum smooth_l1(e)) and ``overflow`` int32 [1]."""
+
+    def __init__(self, cap, device):
+        self.cap = int(cap)
+        self.rows = torch.zeros((4, self.cap), dtype=torch.float32, device=device)
+        self.pred, self.target, self.err = self.rows[0], self.rows[1], (self.rows[2], self.rows[3])
+        self.cursor = torch.zeros(1, dtype=torch.int64, device=device)
+        self.sums = torch.zeros(4, dtype=torch.float64, device=device)
+        self.overflow = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def reset(self):
+        self.cursor.zero_()
+        self.sums.zero_()
+        self.overflow.zero_()
+
+
+def eval_terms_tensor(pred_c, target, heads, buf, pair_weights=None):
+    """``eval_terms`` in tensor ops (the CPU path, the route of a batch the kernel refuses, and the restatement the kernel
+    is tested against).  The definition (see ``eval_terms``): real pairs = nonzero ``pair_weights``; their rows, compacted
+    in batch order, start at ``buf.cursor``; rows at or beyond ``buf.cap`` are dropped and raise ``buf.overflow``.  The
+    boolean gather reads the number of real pairs back on a device: not for a recording."""
+    p, t = F.relu(pred_c.detach().reshape(-1)), target.reshape(-1).to(pred_c.dtype)
+    n = p.numel()
+    real = torch.ones(n, dtype=torch.bool, device=p.device) if pair_weights is None else pair_weights.reshape(-1) != 0
+    row = buf.cursor + torch.cumsum(real, 0) - 1
+    keep = real & (row < buf.cap)
+    dest = row[keep]
+    buf.pred[dest] = p[keep].to(buf.pred.dtype)
+    buf.target[dest] = t[keep].to(buf.target.dtype)
+    for k, head in enumerate(heads or ()):
+        if head is not None:
+            pred, w = head
+            err = (F.relu(pred.detach()) - w.reshape(pred.shape).to(pred.dtype)).abs().sum(dim=1)
+            buf.err[k][dest] = err[keep].to(buf.err[k].dtype)
+    e = (p - t)[real].double()               # the difference in the predictions' own precision, as torch forms it, then widened
+    a = e.abs()
+    count = real.sum()
+    buf.sums += torch.stack([count.double(), a.sum(), (e * e).sum(), torch.where(a < 1, 0.5 * e * e, a - 0.5).sum()])
+    buf.overflow |= (buf.cursor + count > buf.cap).to(buf.overflow.dtype)
+    buf.cursor += count
+    return buf.sums
+
+
+def eval_terms(pred_c, target, heads, buf, pair_weights=None):
+    """What one evaluation batch leaves in ``buf`` (``EvalBuffers``), with no host read: for the REAL pairs (nonzero
+    ``pair_weights`` [n], None: every pair; a 0 marks an inert pair of a padded batch, anywhere in the batch), compacted
+    in batch order at rows ``cursor .. cursor + real - 1``,
+
+        pred[row] = relu(pred_c[i])    target[row] = target[i]    err[k][row] = sum_j |relu(pred_k[i, j]) - float(w_k[i, j])|
+
+    for each of the up to two ``heads`` (``(pred [n, Lc], weights [n, Lc])`` or None; k = 0 node, 1 edge; the sum runs
+    over the whole padded row and masks nothing: train.py:952,967), ``sums`` grows by the real pairs' (1, |e|, e^2,
+    smooth_l1(e)) with e = relu(pred_c) - target formed in fp32 and summed in fp64, and ``cursor`` advances by the
+    number of real pairs.  Rows at or beyond ``buf.cap`` are not written; they raise ``buf.overflow``.  Returns ``buf.sums``.
+    On the GPU in fp32 with int64 weights it is one launch of ``dmp_eval_terms`` (one workgroup, fixed summation order);
+    anything else, and a batch the kernel refuses (more than 2^22 pairs), goes through ``eval_terms_tensor``."""
+    heads = tuple(heads or ())
+    if len(heads) > 2:
+        raise ValueError("eval_terms: at most two matching heads (node, edge)")
+    heads = (heads + (None, None))[:2]
+    n = pred_c.numel()
+    cuda32 = lambda x: x.is_cuda and x.dtype == torch.float32
+    if (cuda32(pred_c) and cuda32(target) and target.numel() == n and buf.rows.is_cuda and n <= 1 << 22
+            and (pair_weights is None or (cuda32(pair_weights) and pair_weights.numel() == n))
+            and all(h is None or (cuda32(h[0]) and h[0].dim() == 2 and h[0].size(0) == n and 1 <= h[0].size(1) <= 1 << 30 and h[1].is_cuda
+                                  and h[1].dtype == torch.int64 and h[1].numel() == h[0].numel()) for h in heads)):
+        from . import _lib
+        lib = _lib.load()
+        p, t = pred_c.detach().reshape(-1).contiguous(), target.reshape(-1).contiguous()
+        pw = None if pair_weights is None else pair_weights.detach().reshape(-1).contiguous()
+        args, keep = [], [p, t, pw]
+        for k, h in enumerate(heads):
+            if h is None:
+                args += [None, 0, None, 0, None]
+                continue
+            hp, hw = h[0].detach(), h[1].reshape(h[0].shape).contiguous()
+            if hp.stride(1) != 1 or hp.stride(0) < hp.size(1):
+                hp = hp.contiguous()
+            keep += [hp, hw]
+            args += [_lib.ptr(hp), hp.stride(0), _lib.ptr(hw), hp.size(1), _lib.ptr(buf.err[k])]
+        _lib.require_gpu(*keep, buf.rows, buf.cursor, buf.sums, buf.overflow)
+        moved = 12 * n + sum(12 * h[0].numel() for h in heads if h is not None)
+        with _lib.timed("eval_terms[n=%d]", (n,), moved):
+            rc = lib.dmp_eval_terms(_lib.ptr(p), _lib.ptr(t), _lib.ptr(pw), n, *args, _lib.ptr(buf.cursor), buf.cap, _lib.ptr(buf.pred),
+                                    _lib.ptr(buf.target), _lib.ptr(buf.sums), _lib.ptr(buf.overflow), _lib.stream_ptr())
+        if rc != -2:        # DMP_ERR_UNSUPPORTED: the tensor ops below
+            _lib.check(rc, "dmp_eval_terms")
+            return buf.sums
+    return eval_terms_tensor(pred_c, target, heads, buf, pair_weights)
+
+
+class GraphedEvalStep(_RecordedStep):
+    """The forward-only twin of ``GraphedTrainStep``: one batch of ``evaluate_epoch`` (collate, the model's forward in eval
+    mode without a gate capacity, with ``match_weights`` the subisomorphism weights, ``eval_terms``) as ONE HIP graph per
+    batch shape.  Nothing of a batch is read on the host: predictions, counts and per-pair matching errors collect in
+    result buffers on the device behind a device-side cursor, the metrics' sums in four fp64 accumulators
+    (``EvalBuffers``); ``evaluate_epoch(graph=step)`` reads them once at the end of the pass.  Padding, the LRP view's
+    permutation capacities and the refusals are ``GraphedTrainStep``'s.  On a CPU device the step runs directly.
+
+    The buffers, the cursor and the sums are state the recorded function updates in place -- as a training step updates
+    the parameters --, NOT arguments of it: ``dp.StepGraph`` copies an argument into a buffer of the recording's own, so a
+    result written through an argument would stay in that copy, and a cursor passed as one would be overwritten by the
+    caller's before every replay.  ``begin`` keeps the buffers while they are large enough; when a pass needs more rows it
+    allocates larger ones and drops the recordings, which hold the old addresses (they are made again, one per shape).
+    ``steps_like``: the ``dp.StepGraph`` of the run's training step -- this object's recordings then share its side
+    stream, so a loop that trains and evaluates under one ``on_stream()`` meets one side stream only."""
+
+    _EAGER = "is evaluated eagerly (evaluate_epoch without graph=...)"
+
+    def __init__(self, model, eval_metric="MAE", max_shapes=4, pad="auto", match_weights=(), steps_like=None):
+        if eval_metric not in _CRIT:
+            raise ValueError("GraphedEvalStep: eval_metric %r (one of %s)" % (eval_metric, ", ".join(_CRIT)))
+        self._init_shared(model, max_shapes, pad, match_weights)
+        self.eval_metric = eval_metric
+        self._steps_like = steps_like
+        self.buffers = None
+        self.heads_seen = [False, False]
+        self.steps = self._new_steps()
+
+    def _new_steps(self):
+        from .dp import StepGraph
+        old = getattr(self, "steps", None)                       # recordings are dropped, the side stream is kept
+        stream = self._steps_like.stream if self._steps_like is not None else (old._stream if old is not None else None)
+        return StepGraph(self._step, max_shapes=self.max_shapes, stream=stream)
+
+    def on_stream(self, device=None):
+        """``steps.on_stream()`` for a pass on a GPU (``device``, or where the buffers live); nothing on a CPU device."""
+        import contextlib
+        cuda = torch.device(device).type == "cuda" if device is not None else (self.buffers is not None and self.buffers.rows.is_cuda)
+        return self.steps.on_stream() if cuda else contextlib.nullcontext()
+
+    def begin(self, n_rows, device):
+        """Start a pass of ``n_rows`` pairs (call it under ``on_stream(device)``, as the batches): cursor, sums and overflow
+        word zeroed; the result buffers are kept while they hold ``n_rows`` rows on ``device`` and regrown (the recordings
+        dropped with them) when they do not."""
+        device = torch.device(device)
+        buf = self.buffers
+        if buf is None or buf.cap < n_rows or buf.rows.device.type != device.type or (device.index is not None and buf.rows.device.index != device.index):
+            self.buffers = EvalBuffers(n_rows, device)
+            self.steps = self._new_steps()
+        else:
+            buf.reset()
+        self.model.eval()
+
+    def _step(self, meta, *tensors):
+        pattern, graph = self.dataset_cls.graphs_from_arrays(meta, tensors)
+        n = 2 * self.dataset_cls.ARRAYS_PER_GRAPH
+        counts = tensors[n]
+        subs = tensors[-2:] if self.match_weights else ()       # (sub_flat at the dataset's capacity, sample_ptr)
+        weights = tensors[n + 1] if len(tensors) == n + 2 + len(subs) else None     # a padded batch: 0 for the inert pairs
+        model = self.model
+        # no optimizer step here that could drop a batch which does not fit a gate capacity: every edge row as it stands
+        cap, model.gate_capacity = getattr(model, "gate_capacity", None), None
+        try:
+            with torch.no_grad():
+                out = model(pattern, graph)
+                heads = [None, None]
+                if subs:
+                    found = self._subiso(meta, pattern, graph, subs)
+                    for k, (w, pk, refine) in enumerate(zip(found, ("pred_v", "pred_e"), (model.refine_node_weights, model.refine_edge_weights))):
+                        if w is not None and out[pk] is not None:
+                            heads[k] = (out[pk], refine(w))
+                self.heads_seen = [h is not None for h in heads]       # a property of the model, the same for every batch
+                return eval_terms(out["pred_c"], counts, heads, self.buffers, pair_weights=weights)
+        finally:
+            model.gate_capacity = cap
+
+    def __call__(self, dataset, indices, device):
+        """One batch of the pass ``begin`` started; returns the sums (device, still growing)."""
+        if self.buffers is None:
+            raise RuntimeError("GraphedEvalStep: begin(n_rows, device) starts a pass")
+        if self.model.training:
+            self.model.eval()
+        meta, tensors = dataset.batch_arrays(indices, device, **self._batch_kwargs(dataset, indices))
+        if tensors[0].is_cuda:
+            return self.steps(meta, *tensors)
+        return self._step(meta, *tensors)
+
+    def results(self, expected, collect=True):
+        """The pass's outcome, read once: ``(sums [4] float64 on the host, rows)`` with ``rows`` = ``[4, expected]`` fp32 on the
+        host (``EvalBuffers.rows``' layout) or None without ``collect``.  ``RuntimeError`` when the cursor is not
+        ``expected`` or the overflow word is set."""
+        buf = self.buffers
+        state = torch.cat([buf.sums, buf.cursor.double(), buf.overflow.double()]).cpu()       # 48 bytes: one read
+        if int(state[5]) != 0:
+            raise RuntimeError("GraphedEvalStep: the pass wrote %d rows into result buffers of %d" % (int(state[4]), buf.cap))
+        if int(state[4]) != int(expected) or int(state[0]) != int(expected):
+            raise RuntimeError("GraphedEvalStep: %d result rows (%d pairs counted) for a dataset of %d pairs"
+                               % (int(state[4]), int(state[0]), int(expected)))
+        return state[:4], (buf.rows[:, :int(expected)].cpu() if collect else None)
+
+
+def _evaluate_recorded(step, dataset, batch_size, device, eval_metric, match_weights, collect):
+    """``evaluate_epoch`` through a ``GraphedEvalStep``."""
+    if isinstance(match_weights, str):
+        match_weights = match_weights.split(",")
+    if match_weights is not None and tuple(w for w in ("node", "edge") if w in match_weights) != step.match_weights:
+        raise ValueError("evaluate_epoch(graph=step): the step was built with match_weights=%r" % (step.match_weights,))
+    if step.match_weights and not all(x.get("subisomorphisms") is not None for x in dataset.samples):
+        raise ValueError("evaluate_epoch(graph=step): the step computes matching errors and a sample has no subisomorphisms")
+    model = step.model
+    cap, model.gate_capacity = getattr(model, "gate_capacity", None), None
+    try:
+        with step.on_stream(device):
+            step.begin(len(dataset), device)
+            for i in range(0, len(dataset), batch_size):
+                step(dataset, np.arange(i, min(i + batch_size, len(dataset))), device)
+            sums, rows = step.results(len(dataset), collect)      # the pass's only reads: under on_stream (dp.StepGraph)
+    finally:
+        model.gate_capacity = cap
+    count = max(float(sums[0]), 1.0)
+    res = {"MAE": float(sums[1]) / count, "MSE": float(sums[2]) / count}
+    res["eval_metric"] = float(sums[{"MAE": 1, "MSE": 2, "SMSE": 3}[eval_metric]]) / count
+    res["RMSE"] = res["MSE"] ** 0.5
+    if rows is not None:
+        res["pred"], res["counts"] = rows[0].clone(), rows[1].clone()
+        res["AUC"] = binary_auc(res["counts"] > 0, res["pred"] > 0)
+        for k, (key, mean) in enumerate((("NED", "MNED"), ("EED", "MEED"))):
+            if step.heads_seen[k]:
+                res[key] = rows[2 + k].clone()
+                res[mean] = float(res[key].mean())
+    return res
+
+
 @torch.no_grad()
-def evaluate_epoch(model, dataset, batch_size, device, eval_metric="MAE", match_weights=None):
+def evaluate_epoch(model, dataset, batch_size, device, eval_metric="MAE", match_weights=None, graph=None, collect=True):
     """train.py:847-1061: MAE / MSE / RMSE of ``relu(pred_c)``, the AUC of ``relu(pred_c) > 0`` against ``counts > 0``
     and the predictions themselves.  With ``match_weights`` ("node", "edge" or both; every sample needs its
     ``subisomorphisms``) and a model whose heads return weights, also the matching half: per pair ``NED`` / ``EED`` = the
     sum of ``|relu(pred) - weights|`` over the whole padded row (train.py:952,967 mask nothing there), their means
     ``MNED`` / ``MEED``, and flat ``pred_v`` / ``pred_e`` / ``node_weights`` / ``edge_weights``: every pair's live
-    positions back to back."""
+    positions back to back.
+    ``graph``: a ``GraphedEvalStep`` built for ``model`` -- every batch then goes through ``dataset.batch_arrays`` and the step
+    (one HIP graph replay per recorded batch shape), nothing is read per batch, and the scalars come from the step's fp64
+    sums; the matching half is the step's own ``match_weights``.  With ``collect`` (the default) ``pred``, ``counts`` and
+    ``NED`` / ``EED`` arrive in ONE copy at the end of the pass and ``AUC`` / ``MNED`` / ``MEED`` are computed from them;
+    ``collect=False`` returns ``MAE`` / ``MSE`` / ``RMSE`` / ``eval_metric`` only, from one read of a few numbers.  The flat
+    live-position lists (``pred_v``, ``pred_e``, ``node_weights``, ``edge_weights``) are NOT produced on this route: their
+    lengths depend on the data (``evaluate_run``, which writes them, evaluates eagerly).  A pass whose row count does not
+    come out at ``len(dataset)`` raises ``RuntimeError``."""
+    if graph is not None:
+        if graph.model is not model:
+            raise ValueError("evaluate_epoch(graph=step): the step was built for another model")
+        return _evaluate_recorded(graph, dataset, batch_size, device, eval_metric, match_weights, collect)
     model.eval()
     preds, targets = [], []
     if isinstance(match_weights, str):
@@ -1115,13 +1384,16 @@ def validate_samples(samples):
 
 
 def fit(model, optimizer, train_set, dev_set, epochs, batch_size, device, save_dir=None, config=None, sync=None,
-        eval_metric="MAE", seed=0, **train_kw):
+        eval_metric="MAE", seed=0, eval_graph=False, **train_kw):
     """The epoch loop of ``train.py:1296-1380`` reduced to its contract: per epoch one shuffled training
     pass and one dev evaluation; with ``save_dir`` the run directory the reference's tooling expects --
     ``config.json``, ``epoch%d.pt`` (state dict of every epoch), ``log.txt`` whose "best" lines
     (``utils/log.py:50-57``) ``dataio.get_best_epochs`` reads back.  Returns the per-epoch history.
     ``graph=True`` (with ``FlatAdamW(capturable=True)``, one rank): training steps whose batch shape repeats are
     recorded once and replayed as one HIP graph (``GraphedTrainStep``).
+    ``eval_graph=True``: when ``graph`` resolved to a recorded training step, the dev pass is recorded too
+    (``GraphedEvalStep`` on the training recordings' side stream, ``evaluate_epoch(graph=..., collect=False)``: one read of
+    a few numbers per epoch); without a recorded training step the dev pass runs eagerly, as ``graph=True`` falls back.
     ``gate_compact=True`` (or a margin, e.g. 1.25): training forward passes run the rep-net on the target edges the filter
     gate keeps (``model.set_gate_capacity``; capacity = the largest kept count over the training batches in their stored order x the margin; batches are shuffled in training, so a batch can still exceed it: such steps are dropped, counted, and a warning is raised above 1 % of the steps).
     A batch that keeps more than that raises a device flag and the optimizer drops its step (``FlatAdamW.set_veto``, as a
@@ -1181,12 +1453,15 @@ def fit(model, optimizer, train_set, dev_set, epochs, batch_size, device, save_d
     graphed = train_kw.get("graph")
     # recorded steps: the whole loop (evaluation, checkpoint copies) on the recordings' side stream -- see dp.StepGraph
     stream_ctx = graphed.steps.on_stream() if graphed else contextlib.nullcontext()
+    dev_kw = {}
+    if eval_graph and isinstance(graphed, GraphedTrainStep):
+        dev_kw = {"graph": GraphedEvalStep(model, eval_metric=eval_metric, steps_like=graphed.steps), "collect": False}
     try:
       with stream_ctx:
         for epoch in range(epochs):
             tr = train_epoch(model, optimizer, train_set, batch_size, device, sync=sync, eval_metric=eval_metric,
                              order=rng.permutation(len(train_set)), **dict(train_kw, epoch=epoch))
-            dev = evaluate_epoch(model, dev_set, batch_size, device, eval_metric=eval_metric)
+            dev = evaluate_epoch(model, dev_set, batch_size, device, eval_metric=eval_metric, **dev_kw)
             history.append({"epoch": epoch, "train": tr, "dev": {k: dev[k] for k in ("MAE", "MSE", "eval_metric")}})
             if getattr(model, "gate_capacity", None):
                 history[-1]["dropped_steps"] = model.compaction_dropped_steps()       # cumulative (one host sync per epoch)

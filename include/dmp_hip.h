@@ -1778,6 +1778,25 @@ int dmp_collate_resident(const dmp_resident_side *store, const float *counts, co
                          float *o_weights, int64_t *sub_flat, int64_t sub_capacity, int64_t sub_total, int64_t *sample_ptr,
                          void *stream);
 
+/* ---- What an evaluation batch leaves behind, on the device, with no host read (dmp_evalterms.hip; train.py:847-1061 per batch:
+ * relu(pred_c) and the counts appended to lists, train.py:952,967's per-pair matching errors, the error sums of the metrics).
+ *   pred_c / target [n] fp32;  pair_w [n] fp32 0 / 1 or NULL (every pair real; 0 = an inert pair of a padded batch, anywhere
+ *   in the batch);  per matching head (v: node, e: edge; a NULL pred_* = no such head) pred [n, Lc] fp32 with row stride
+ *   ld >= Lc, w [n, Lc] int64, err_* [cap];
+ *   cursor: DEVICE int64, the result rows written so far in this pass;  cap: the rows of pred_out / target_out / err_*.
+ * The real pairs, compacted in batch order, land at rows cursor .. cursor + real - 1:
+ *   pred_out[row] = max(pred_c[i], 0)   target_out[row] = target[i]   err_*[row] = sum_j |max(pred[i, j], 0) - float(w[i, j])|
+ * (the whole padded row, nothing masked; fp32), and with e = fl32(max(pred_c[i], 0) - target[i]) widened to fp64 the DEVICE
+ * double sums[4] grow by the real pairs' (1, |e|, e^2, smooth_l1(e) with beta 1).  Last, *cursor += real: a replayed
+ * recording needs nothing from the host.  Rows at or beyond cap are never written; cursor + real > cap sets *overflow = 1
+ * (int32, never cleared here) and the cursor still advances.  One launch, one workgroup, no atomics, fixed summation order
+ * (bit-stable); launches of one pass must be ordered by their stream.  n <= 2^22 and Lc <= 2^30, else DMP_ERR_UNSUPPORTED
+ * (the caller uses its tensor ops). */
+int dmp_eval_terms(const float *pred_c, const float *target, const float *pair_w, int64_t n, const float *pred_v, int64_t ld_v,
+                   const int64_t *w_v, int64_t Lc_v, float *err_v, const float *pred_e, int64_t ld_e, const int64_t *w_e,
+                   int64_t Lc_e, float *err_e, int64_t *cursor, int64_t cap, float *pred_out, float *target_out, double *sums,
+                   int32_t *overflow, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
