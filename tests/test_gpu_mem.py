@@ -3,6 +3,8 @@
 * kernel forward (memory and memory mask) and backward against an fp64 restatement (``mem.memory_tensor`` in double)
   over a sweep of lengths, widths, memory lengths, pooling modes, circular extension, both end rules and mask shapes
   (front padding, interior holes, masked last positions, all-masked and single-live pairs), one and two tensors;
+* max pooling where rows tie (rows of -1 / 0 / 1): kernels and the device's tensor-op route against the explicit-loop
+  restatement of tests/test_mem_ties_cpu.py -- the value and the gradient go to the window's first maximum;
 * bitwise reproducibility, every output written (DMP_POISON_DEAD_ROWS), the dispatch to the tensor-op path;
 * the fixtures of scripts/make_golden_mem.py (the reference's own runs) with the tensor-op memory and attention paths
   monkeypatched to raise: init_memory, MemDotAttention, the four heads standalone, DMPNN + DIAMNet and RGIN +
@@ -104,6 +106,58 @@ def test_kernel_matches_fp64(mem_init, inclusive, gpu):
         for y, ry, dx, rdx in zip(ys, rys, dxs, rdxs):
             _close(y, ry, 1e-5, what + " memory")
             _close(dx, rdx, 1e-5, what + " dX")
+
+
+TIE_SWEEP = [(4, 40, 8, 3, True), (4, 33, 4, 1, False), (5, 7, 8, 4, True), (4, 300, 12, 4, False)]   # (B, L, D, M, two tensors)
+
+
+def _tied_windows(mem_init, inclusive, gpu, width=None):
+    """Rows of -1 / 0 / 1 (tests/test_mem_ties_cpu.py): a window's value and gradient belong to its first maximum in
+    extended-row order.  Memory and memory mask bitwise (a maximum of exact integers is exact), dX at the file's 1e-5.
+    ``width``: that many columns instead of the case's."""
+    from test_mem_ties_cpu import TIED_SHARE, tie_case, tie_grads, tie_reference
+    long_cells = long_tied = 0
+    for B, L, D, M, two in TIE_SWEEP:
+        D = width or D
+        xs, g = tie_case(B, L, D, two, zlib.crc32(repr((B, L, D, M, mem_init, inclusive)).encode()))
+        mask = _masks(B, L, g)
+        dys = tie_grads(xs, M, g)
+        rys, rmm, rdxs, counts = tie_reference(xs, mask, M, mem_init, inclusive, dys)
+        ys, mm, dxs = _run(xs, mask, M, mem_init, inclusive, dys, gpu)
+        what = "%s L%d D%d M%d" % (mem_init, L, D, M)
+        print("MEMTIES %s inclusive %d: tied %d of %d cells with two or more rows, %d of %d with 14 or more"
+              % (what, inclusive, counts[1], counts[0], counts[3], counts[2]))
+        long_cells, long_tied = long_cells + counts[2], long_tied + counts[3]
+        assert th.equal(mm.cpu(), rmm), what + " memory mask"
+        for y, ry, dx, rdx in zip(ys, rys, dxs, rdxs):
+            assert th.equal(y.detach().cpu().double(), ry), what + " memory"
+            _close(dx, rdx, 1e-5, what + " dX")
+    # windows of 14 rows and more give each of the four waves several rows: ties inside a wave and between waves
+    assert long_cells > 0 and long_tied >= TIED_SHARE * long_cells, (long_tied, long_cells)
+
+
+@pytest.mark.parametrize("inclusive", [False, True])
+@pytest.mark.parametrize("mem_init", ["max", "circular_max"])
+def test_kernel_gives_a_tied_window_to_its_first_maximum(mem_init, inclusive, gpu, monkeypatch):
+    from dualmessagepassing_amd import mem
+    calls = []
+    orig = mem.MemInit.apply
+    monkeypatch.setattr(mem.MemInit, "apply", lambda *a: (calls.append(1), orig(*a))[1])
+    monkeypatch.setattr(mem, "memory_tensor", None)                    # (not callable: the tensor-op route would raise)
+    _tied_windows(mem_init, inclusive, gpu)
+    assert len(calls) == len(TIE_SWEEP), "the kernels were not taken"
+
+
+@pytest.mark.parametrize("inclusive", [False, True])
+@pytest.mark.parametrize("mem_init", ["max", "circular_max"])
+def test_tensor_op_route_on_the_device_gives_a_tied_window_to_its_first_maximum(mem_init, inclusive, gpu, monkeypatch):
+    """Width 6 is no multiple of 4: ``mem.memory_tensor`` on the device."""
+    from dualmessagepassing_amd import mem
+    calls = []
+    orig = mem.memory_tensor
+    monkeypatch.setattr(mem, "memory_tensor", lambda *a: (calls.append(1), orig(*a))[1])
+    _tied_windows(mem_init, inclusive, gpu, width=6)
+    assert len(calls) == len(TIE_SWEEP), "the tensor-op route was not taken"
 
 
 def test_kernel_is_bitwise_reproducible(gpu):

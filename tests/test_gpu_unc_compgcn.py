@@ -1,6 +1,9 @@
 """CompGCN on the kernels (``unc_compgcn``): ``dmp_relcorr_weights_fwd`` / ``_bwd`` against the fp64 restatement with explicit
-circulants (tests/util_fp64_compgcn.py) at every admitted corner -- I != H, I no power of two with padding columns, the
-maximum -- bitwise repeatable, and a refused shape that must fall back; every reference fixture on the kernel path; the kernel
+circulants (tests/util_fp64_compgcn.py) over ``FORMER_SHAPES`` -- the smallest and the largest admitted size; I != H, I no
+power of two with padding columns; each of the three routes of the dT gradient (one, two or four column groups: H <= 64,
+H <= 128, above) with full and with partial last groups; one and several column tiles with a partial last one (H 65, 129,
+130, 200); I no multiple of 8 at H > 64; I far below and far above H at R = 16 -- bitwise repeatable, and a refused shape that
+must fall back; every reference fixture on the kernel path; the kernel
 path against the tensor-op path of the same module on a 2,000-node graph with edge types outside the table; replayed
 training against the eager loop.
 
@@ -80,7 +83,20 @@ def _former_case(I, H, R, gpu, calls, repeatable=True):
     return got
 
 
-@pytest.mark.parametrize("I,H,R", [(4, 4, 1), (12, 8, 2), (50, 50, 2), (64, 64, 8), (256, 256, 16)])
+FORMER_SHAPES = [
+    (4, 4, 1), (12, 8, 2), (50, 50, 2), (64, 64, 8), (256, 256, 16),
+    # dT over two column groups (64 < H <= 128), each taking half of the rows
+    (40, 100, 3), (100, 72, 2), (13, 128, 1),
+    (72, 65, 4),             # P = 68: the second column tile has one live column
+    (5, 64, 1),              # the widest H on the one-group route, I below a lane's 8 rows
+    # dT over four column groups with a partial last one; more than one column tile, the last one partial; I % 8 != 0
+    (64, 129, 1), (30, 130, 2), (255, 200, 3),
+    (9, 255, 16),            # I << H at the largest R
+    (256, 5, 16),            # I >> H: the largest backward LDS at a narrow width
+]
+
+
+@pytest.mark.parametrize("I,H,R", FORMER_SHAPES)
 def test_relcorr_weights_match_fp64_and_are_repeatable(I, H, R, gpu, monkeypatch):
     from dualmessagepassing_amd import _lib
     calls = _spy(monkeypatch)
