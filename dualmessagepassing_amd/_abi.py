@@ -34,6 +34,10 @@ DMP_LRP_MAX_SEQ_LEN = 6
 DMP_LRP_OVER_CAP, DMP_LRP_SELF_LOOP, DMP_LRP_DROPPED = 1, 2, 4      # bits of the status word of dmp_lrp_count / _fill
 DMP_RANK_BAD_TYPE = 1                                  # status word of dmp_rank_counts_typed: a type code above 62 was met
 DMP_RESIDENT_MAX_SLOTS = 4096                          # pairs (real + inert) of a batch dmp_collate_resident assembles
+DMP_SUBISO_MAX_PN, DMP_SUBISO_MAX_PM = 16, 64          # the pairs dmp_subiso_label_dev admits: pattern nodes / edges,
+DMP_SUBISO_MAX_GN, DMP_SUBISO_MAX_GM = 512, 2048       # graph nodes / distinct (src, dst, label) graph edges
+DMP_SUBISO_MAX_BUDGET = 16777216                       # the largest trial budget of one of its work items
+DMP_SUBISO_DESC_WORDS = 8                              # int32 words of a pair's row in dmp_subiso_image.desc
 
 
 # ---- the structs, named and ordered as in the header; pointers are c_void_p (assigned from ``data_ptr()`` / None)
@@ -157,6 +161,13 @@ class dmp_resident_side(ctypes.Structure):
 class dmp_resident_batch(ctypes.Structure):
     _fields_ = [("src", c_ptr), ("dst", c_ptr), ("num_nodes", c_ptr), ("num_edges", c_ptr), ("nid", c_ptr), ("vlabel", c_ptr), ("eid", c_ptr),
                 ("elabel", c_ptr), ("rev", c_ptr)]
+
+
+class dmp_subiso_image(ctypes.Structure):
+    _fields_ = [("desc", c_ptr), ("p_cbeg", c_ptr), ("p_cend", c_ptr), ("p_tend", c_ptr), ("p_ends", c_ptr), ("p_elab", c_ptr),
+                ("g_rowptr", c_ptr), ("g_ent", c_ptr), ("g_cand", c_ptr), ("g_inv", c_ptr), ("chunk_pair", c_ptr), ("chunk_root", c_ptr),
+                ("num_pairs", c_i64), ("total_pn", c_i64), ("total_pm", c_i64), ("total_gn", c_i64), ("total_gm", c_i64),
+                ("total_um", c_i64), ("num_chunks", c_i64), ("max_gn", c_int), ("max_um", c_int)]
 
 
 _p = ctypes.POINTER      # ``const dmp_X *``: takes an array ``(dmp_X * n)()``, ``byref(x)`` or None, nothing else
@@ -422,6 +433,7 @@ SIGNATURES = {
                                  c_ptr, c_ptr, c_ptr, c_ptr]),
     "dmp_collate_resident": (c_int, [_p(dmp_resident_side), c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, _p(dmp_resident_batch), c_ptr, c_ptr,
                                      c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
+    "dmp_subiso_label_dev": (c_int, [_p(dmp_subiso_image), c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "dmp_eval_terms": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
                                c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
 }

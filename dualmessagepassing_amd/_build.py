@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libdmp_hip.so")
 HASH_PATH = LIB_PATH + ".srchash"
-SOURCES = ["dmp_agg.hip", "dmp_segacc.hip", "dmp_compact.hip", "dmp_graph.hip", "dmp_fused.hip", "dmp_mfma.hip", "dmp_typed.hip", "dmp_h1w.hip", "dmp_nodechain.hip", "dmp_edgemlp.hip", "dmp_l0mlp.hip", "dmp_l0node.hip", "dmp_atb.hip", "dmp_fold.hip", "dmp_heads.hip", "dmp_layer0.hip", "dmp_bn.hip", "dmp_attn.hip", "dmp_mem.hip", "dmp_cnn.hip", "dmp_rnn.hip", "dmp_relconv.hip", "dmp_relcorr.hip", "dmp_txl.hip", "dmp_match.hip", "dmp_lrp.hip", "dmp_rank.hip", "dmp_rank_typed.hip", "dmp_lrppool.hip", "dmp_resident.hip", "dmp_evalterms.hip",
+SOURCES = ["dmp_agg.hip", "dmp_segacc.hip", "dmp_compact.hip", "dmp_graph.hip", "dmp_fused.hip", "dmp_mfma.hip", "dmp_typed.hip", "dmp_h1w.hip", "dmp_nodechain.hip", "dmp_edgemlp.hip", "dmp_l0mlp.hip", "dmp_l0node.hip", "dmp_atb.hip", "dmp_fold.hip", "dmp_heads.hip", "dmp_layer0.hip", "dmp_bn.hip", "dmp_attn.hip", "dmp_mem.hip", "dmp_cnn.hip", "dmp_rnn.hip", "dmp_relconv.hip", "dmp_relcorr.hip", "dmp_txl.hip", "dmp_match.hip", "dmp_lrp.hip", "dmp_rank.hip", "dmp_rank_typed.hip", "dmp_lrppool.hip", "dmp_resident.hip", "dmp_evalterms.hip", "dmp_subiso_dev.hip",
            "dmp_subiso.cpp"]   # the last one: host-only C++ (exact subgraph-isomorphism counter), same C ABI
 HEADERS = ["dmp_common.h", "dmp_mfma_common.h", "dmp_x6_tile.h", "dmp_rank_kernel.h", os.path.join("..", "..", "include", "dmp_hip.h")]
 ARCH = "gfx950"

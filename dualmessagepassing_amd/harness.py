@@ -487,9 +487,11 @@ class SmallLikePairs(PairDataset):
     free graph nodes); a graph is directed ER noise with uniform labels into which 0 .. 12 copies of its pattern are
     planted (node labels overwritten, the pattern's edges added), so that counts are mostly small positive numbers instead
     of zeros and rare explosions.  Counts are EXACT whatever the planting did: they come from the native search over a
-    pool of host threads (``count_subisomorphisms_batch``); the enumerations themselves are not kept (count loss only)."""
+    pool of host threads (``count_subisomorphisms_batch``) or, with a ``device``, from the device search
+    (``subiso.label_pairs``: the same counts, so a seed yields the same samples either way); the enumerations themselves are
+    not kept (count loss only)."""
 
-    def __init__(self, num_pairs, seed=0, threads=0):
+    def __init__(self, num_pairs, seed=0, threads=0, device=None):
         rng = np.random.default_rng(seed)
         self.shape = dict(p_nodes=8, p_edges=8, g_nodes=64, g_edges=256, n_vlabels=16, n_elabels=16)
         raw = []
@@ -527,7 +529,11 @@ class SmallLikePairs(PairDataset):
             gu, gv = (np.array(x, np.int64) for x in zip(*keys))
             gel = np.array([edges[k] for k in keys], np.int64)
             raw.append((pu, pv, pvl, pel, gu, gv, gvl, gel))
-        counts = count_subisomorphisms_batch(raw, threads)
+        if device is None:
+            counts = count_subisomorphisms_batch(raw, threads)
+        else:
+            from .subiso import label_pairs
+            counts = label_pairs(raw, device, threads=threads)["counts"]
         self.samples = []
         for (pu, pv, pvl, pel, gu, gv, gvl, gel), c in zip(raw, counts):
             self.samples.append({"pattern": self._with_rev(pu, pv, pvl, pel, 8, 16), "graph": self._with_rev(gu, gv, gvl, gel, 256, 16),

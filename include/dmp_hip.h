@@ -1797,6 +1797,51 @@ int dmp_eval_terms(const float *pred_c, const float *target, const float *pair_w
                    int64_t Lc_e, float *err_e, int64_t *cursor, int64_t cap, float *pred_out, float *target_out, double *sums,
                    int32_t *overflow, void *stream);
 
+/* ---- Labels of (pattern, graph) pairs on the DEVICE (dmp_subiso_dev.hip): per pair the exact number of subisomorphisms, the
+ * number of trials the search made and, optionally, the node / edge weights of the matching loss summed over the matches
+ * without a match row ever being stored.  Semantics and node order are dmp_subiso_enumerate's: nodes placed in id order, a
+ * candidate for node k = a graph node of k's label no earlier node uses, accepted when every pattern edge whose later endpoint
+ * is k has an image edge of its label; a TRIAL is a candidate whose edge checks are evaluated.
+ * The image of a batch, DEVICE arrays the caller prepares (dualmessagepassing_amd/subiso.py does, in numpy, before the upload):
+ *   desc [num_pairs, DMP_SUBISO_DESC_WORDS] : pn, pm, gn, um (the graph's DISTINCT (src, dst, label) edges), then the pair's
+ *            first pattern node, pattern edge, graph node and distinct entry in the flat arrays below
+ *   p_cbeg / p_cend [total_pn] : node k's candidates are g_cand[graph's first node + cbeg .. + cend)
+ *   p_tend [total_pn], p_ends / p_elab [total_pm] : the pair's pattern edges sorted by their later endpoint (ties in edge
+ *            order) as src | dst << 8 and a label code; those whose later endpoint is k end at (pair-local) tend[k]
+ *   g_rowptr [total_gn + 1] : CSR by source over g_ent (indices into g_ent, the batch's nodes back to back)
+ *   g_ent [total_um] : the distinct edges sorted by (pair, src, dst, label) as dst << 32 | label code (pair-local dst; one code
+ *            space for pattern and graph edge labels)
+ *   g_cand [total_gn] : per pair its nodes (pair-local ids) sorted by (label, id)
+ *   g_inv [total_gm] : per original graph edge, in the batch's order, its entry in g_ent
+ *   chunk_pair / chunk_root [num_chunks] : the work list -- a chunk is up to 64 consecutive candidates of pattern node 0 of
+ *            one pair, from candidate chunk_root on; one wave per chunk, a lane per candidate
+ *   max_gn / max_um : the largest gn / um among the pairs to be searched (LDS is sized by them)
+ * Admitted: pn <= DMP_SUBISO_MAX_PN, pm <= DMP_SUBISO_MAX_PM, gn <= max_gn <= DMP_SUBISO_MAX_GN, um <= max_um <=
+ * DMP_SUBISO_MAX_GM.  Any other pair, and a pair whose image holds a value out of its range, comes back complete = 0 without
+ * being searched (no error).  pn = 0 counts 1; a pair without a chunk (pn > gn, no candidate for node 0) counts 0.
+ * budget (1 .. DMP_SUBISO_MAX_BUDGET): the trials ONE work item (pair, candidate of node 0) may make; an item that needs more
+ * stops and clears its pair's `complete`, whose other outputs are then meaningless.  The search loop's trip count is capped at
+ * (budget + 1) * (pn + 2).
+ * Outputs (every element written, nothing read from them before): counts / trials [num_pairs] int64, complete [num_pairs]
+ * uint8, node_weights [total_gn] (per graph node the matches whose image contains it) and edge_weights [total_gm] (per graph
+ * edge k: the sum over matches f and pattern edges (u, v, l) of [src_k = f(u), dst_k = f(v), label_k = l]), each optional
+ * (NULL); workspace [total_um] int64 is needed with edge_weights.  Integer atomics only: run-to-run bit-stable.  A few
+ * launches on `stream` (an init, one search launch per 2048 chunks, an expansion of the entry sums to the edges), no host
+ * synchronisation.  `image` itself is a HOST struct. */
+#define DMP_SUBISO_MAX_PN 16
+#define DMP_SUBISO_MAX_PM 64
+#define DMP_SUBISO_MAX_GN 512
+#define DMP_SUBISO_MAX_GM 2048
+#define DMP_SUBISO_MAX_BUDGET 16777216
+#define DMP_SUBISO_DESC_WORDS 8
+typedef struct {
+  const int32_t *desc, *p_cbeg, *p_cend, *p_tend, *p_ends, *p_elab, *g_rowptr; const int64_t *g_ent;
+  const int32_t *g_cand, *g_inv, *chunk_pair, *chunk_root;
+  int64_t num_pairs, total_pn, total_pm, total_gn, total_gm, total_um, num_chunks; int max_gn, max_um;
+} dmp_subiso_image;
+int dmp_subiso_label_dev(const dmp_subiso_image *image, int64_t budget, int64_t *counts, int64_t *trials, uint8_t *complete,
+                         int64_t *node_weights, int64_t *edge_weights, int64_t *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
